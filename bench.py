@@ -3,6 +3,7 @@
 
   python bench.py --gpus N --steps K --warmup W          (N>1: one rank per GPU under torch.distributed.run -- started by the
                                                           driver, or by bench.py itself when it finds no WORLD_SIZE in its environment)
+  python bench.py ... --dump-outputs DIR                 (also writes the last timed step's outputs as DIR/<name>.npy)
 
 A "step" is one pass of the hot path over one batch of synthetic input: BASELINE config 2 -- B=8 clouds of
 N=8192 points through the Pointnet2MSGSEG-spec encoder (3x SA-MSG: FPS + ball query + grouped shared MLP + max
@@ -16,10 +17,14 @@ the timed region (barrier + synchronize on both sides, max over ranks).
 Multi-GPU: frames are independent -> each rank processes its own batches, no data-path
 collective, weak scaling; value = frames of all ranks / max-over-ranks time.
 
-Timed region: the K steps are repeated R times back to back (`repeats` in the output; R chosen so that the region lasts
->= 0.5 s whatever --steps is, so a short driver run is not a single wave of batches); ms_per_step = time / (K * R).
+Timed region: exactly K = --steps steps, after W = --warmup untimed ones and one untimed replay of every captured call;
+ms_per_step = time / K.  A K that is not a multiple of --coalesce ends on a partially filled call, which runs (and is timed) whole.
 Inputs: every step first copies a fresh batch from a rotating pool of distinct clouds (> 256 MB, i.e. larger than the MALL)
 into the stream's input buffer, so the path reads inputs that are cold in every cache -- the copy is inside the timed region.
+The pool, the pose parameters and the weights are seeded: the same arguments give the same inputs in every run.
+
+--dump-outputs DIR: after the timed region, the outputs of the last timed step (what StepFuture.result() hands its caller:
+sem_logits (8, N, classes) and, with lbs(), verts (8, 6890, 3) and joints (8, J, 3)) are written as DIR/<name>.npy in float32.
 
 Output: ONE JSON line (rank 0) with the contract fields + `roofline` (dominant kernel by GPU time = FPS level 1, a LATENCY-
 bound kernel, measured with HIP events in an instrumented eager pass inside this script) + `roofline_mfma` (heaviest MFMA
@@ -34,11 +39,8 @@ import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
-# The HIP runtime maps streams onto GPU_MAX_HW_QUEUES hardware queues (default 4): with 16 batches in flight on 16
-# streams, 4 queues serialise them four deep (11.8k frames/s, round 1); 32 queues let every stream own one (17.9k).
-# Past ~24 streams they share queues again and the step collapses (profiles/r03_dispatch_cost_by_streams.txt).  Must be
-# set before the runtime initialises, i.e. before torch is imported.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "32")
+# The HIP runtime maps the executor's streams onto the hardware queues the environment allows (GPU_MAX_HW_QUEUES); the
+# bench leaves that setting to the environment it runs in and reports it as config.hw_queues.
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
@@ -60,7 +62,6 @@ def parse():
     ap.add_argument("--no-graph", action="store_true", help="launch eagerly instead of replaying hipGraphs")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-frames", type=int, default=16, help="frames per sample the CPU oracle is timed on with all cores")
-    ap.add_argument("--min-seconds", type=float, default=3.0, help="minimum length of the timed region (the K steps are repeated)")
     ap.add_argument("--input-pool-mb", type=float, default=320.0, help="distinct input clouds rotated through, in MB (0 = replay the "
                                                                        "same resident batches: MALL-warm inputs)")
     ap.add_argument("--no-lbs", action="store_true")
@@ -69,7 +70,11 @@ def parse():
                     help="bf16 = BASELINE config 3: shared-MLP operands in bf16 (fp32 accumulate); default fp32 = config 2")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N>1 (nccl = RCCL; gloo only for "
                                                        "exercising the multi-rank path on a box with fewer GPUs than ranks)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs (rank 0) as DIR/<name>.npy, float32")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def build_workload(device, with_lbs, pool_mb):
@@ -508,6 +513,15 @@ def cpu_frame_parallel(sd, workers, frames_each, with_lbs):
             "max_start_lateness_s": max(r["late"] for r in res)}
 
 
+def dump_outputs(out_dir, fut):
+    """The arrays the executor hands the caller of one step (StepFuture.result()) as out_dir/<name>.npy, float32: sem_logits (8, N, classes)
+    and, with lbs(), verts (8, V, 3) and joints (8, J, 3) -- about 2.5 MB in all."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in zip(("sem_logits", "verts", "joints"), fut.result()):
+        if t is not None:
+            np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
+
+
 def self_launch(ngpus, script, argv):
     """`python bench.py --gpus N` started WITHOUT a launcher: become the launcher.  The reference starts one process per GPU
     (`srun ... python train_temporal.py`, scripts/train/train_tshirt_posed.sh; rank / world size from the environment,
@@ -576,26 +590,28 @@ def main():
 
         def run_steps(first, count):
             """`count` B = 8 steps handed to the executor one at a time; each is the next batch of the input pool (device-to-device copies
-            into the call's input buffers on the call's stream, inside the timed region); a call goes out when `kco` steps are in it."""
+            into the call's input buffers on the call's stream, inside the timed region); a call goes out when `kco` steps are in it.
+            Returns the future of the last step."""
+            fut = None
             for k in range(first, first + count):
                 if pose_pool is None:
-                    pipe.submit(pool[k % npool], inputs_ready=True)
+                    fut = pipe.submit(pool[k % npool], inputs_ready=True)
                 else:
                     bt, ps = pose_pool[k % len(pose_pool)]
-                    pipe.submit(pool[k % npool], bt, ps, inputs_ready=True)
+                    fut = pipe.submit(pool[k % npool], bt, ps, inputs_ready=True)
+            return fut
 
-        run_steps(0, max(args.warmup, 1))                # W untimed warm-up steps (the executor has already run every call once)
+        run_steps(0, args.warmup)                        # W untimed warm-up steps (the executor has already run every call once)
+        run_steps(args.warmup, kco * ns)                 # untimed: the first replay of every captured call
         pipe.synchronize()
+        first = args.warmup + kco * ns                   # the timed steps go on through the pool: their inputs are not the ones just read
 
-        # The K-step block is repeated R times; R grows until the timed region lasts >= --min-seconds (all ranks agree on R and on
-        # "long enough" through the max-reduced time).  Only the last, long-enough run is reported.  Every step submitted inside the region
-        # is finished inside it: a last, partially filled call is flushed (it then runs on stale clouds as well -- R is chosen so that K * R
-        # is a multiple of the coalescing factor and nothing is wasted in the reported run).
-        def timed_block(repeats):
+        # The timed region: exactly K steps, all of them finished inside it (a last, partially filled call is flushed and runs whole, on
+        # the slot's stale tail clouds as well).  With several ranks the region's time is the max over ranks.
+        def timed_block():
             barrier()
             t0 = time.perf_counter()
-            for r in range(repeats):
-                run_steps(r * args.steps, args.steps)
+            fut = run_steps(first, args.steps)
             pipe.synchronize()
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0
@@ -604,27 +620,21 @@ def main():
                 dist.all_reduce(tt, op=dist.ReduceOp.MAX)
                 dt = float(tt.item())
             barrier()
-            return dt
+            return dt, fut
 
-        unit = kco // int(np.gcd(kco, args.steps))       # repeats that make K * R a multiple of the coalescing factor
-        repeats = unit
-        timed_block(repeats)                             # untimed: first replays after capture
-        while True:
-            dt = timed_block(repeats)
-            if dt >= args.min_seconds or repeats >= 1 << 20:
-                break
-            repeats = max(repeats + unit, int(np.ceil(repeats * args.min_seconds / max(dt, 1e-6) * 1.15 / unit)) * unit)
-        # per-rank rate of the reported run (rank 0 prints the spread: a straggling GPU shows here first)
+        dt, last = timed_block()
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, last)        # now: the slot's output buffers are reused by the calls that follow
+        # per-rank rate of the same K steps once more (rank 0 prints the spread: a straggling GPU shows here first)
         my_dt = None
         if dist is not None:
             barrier()
             t0 = time.perf_counter()
-            for r in range(unit):
-                run_steps(r * args.steps, args.steps)
+            run_steps(first, args.steps)
             pipe.synchronize()
             torch.cuda.synchronize()
             my_dt = time.perf_counter() - t0
-            rates = torch.tensor([unit * args.steps * B_CLOUDS / my_dt], device=dev if args.backend == "nccl" else "cpu", dtype=torch.float64)
+            rates = torch.tensor([args.steps * B_CLOUDS / my_dt], device=dev if args.backend == "nccl" else "cpu", dtype=torch.float64)
             gl = [torch.zeros_like(rates) for _ in range(world)]
             dist.all_gather(gl, rates)
             per_rank = [float(t.item()) for t in gl]
@@ -707,7 +717,7 @@ def main():
             except Exception as e:   # a secondary leg must never cost the headline line
                 v_model = None
                 dropin = {"error": f"{type(e).__name__}: {e}"[:300]}
-            ex = args.steps * repeats * B_CLOUDS / dt
+            ex = args.steps * B_CLOUDS / dt
             if v_model is not None:
               dropin = {"value": v_model, "unit": "frames/s", "ratio_to_executor": v_model / ex,
                       "route": "middle, sem_logits, l_features, l_xyz = model(pc) in eval() + torch.no_grad() (the reference's forward contract: (B, C, N) features, "
@@ -726,13 +736,13 @@ def main():
                 table, roof = [], {"roofline": {"error": f"{type(e).__name__}: {e}"[:300]}}
 
     if rank == 0:
-        total_steps = args.steps * repeats
+        total_steps = args.steps
         frames = total_steps * B_CLOUDS * world
         fps = frames / dt
         per_gpu = fps / world
         line = {
             "metric": "point-cloud frames/s (FPS+ball_query+SA-MLP+LBS), B=8 N=8192",
-            "value": fps, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "repeats": repeats,
+            "value": fps, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "timed_seconds": dt, "ms_per_step": dt / total_steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": {"fp32": "f32", "bf16": "bf16 MLP operands / f32 accumulate, sampling, LBS",
                       "bf16x3": "f32 values; shared-MLP products as 6 bf16 x bf16 piece products of exact 3-way operand splits, f32 accumulate (fp32-accurate)"}[args.precision], "data": "synthetic",
@@ -741,11 +751,11 @@ def main():
             "config": {"workload": ("cfg2: B=8 N=8192 Pointnet2MSGSEG-spec encoder (3xSA-MSG + 3xFP + head) fp32" if args.precision == "fp32" else
                                     f"cfg3 precision on the cfg2 step: B=8 N=8192 Pointnet2MSGSEG-spec encoder (3xSA-MSG + 3xFP + head), shared-MLP operands {args.precision}")
                                    + (" + SMPL lbs() of the 8 frames (V=6890,J=24)" if with_lbs else ""),
-                       "frames_per_step": B_CLOUDS, "repeats": repeats, "timed_seconds": dt, "timed_steps": total_steps, "coalesce": kco, "clouds_per_call": B_CLOUDS * kco, "calls_in_flight": ns,
+                       "frames_per_step": B_CLOUDS, "timed_seconds": dt, "timed_steps": total_steps, "coalesce": kco, "clouds_per_call": B_CLOUDS * kco, "calls_in_flight": ns,
                        "batches_in_flight": ns * kco, "hipgraph": not args.no_graph,
                        "executor": "garment4d_amd.pipeline.StepPipeline: steps are submitted one B=8 batch at a time; `coalesce` consecutive steps run as "
                                    "one call on 8*coalesce clouds (bit-identical per cloud), `calls_in_flight` calls overlap on their own streams",
-                       "hw_queues": int(os.environ.get("GPU_MAX_HW_QUEUES", "4")),
+                       "hw_queues": int(os.environ["GPU_MAX_HW_QUEUES"]) if os.environ.get("GPU_MAX_HW_QUEUES") else None,   # None: the runtime's default
                        "inputs": (f"rotating pool of {npool} distinct batches = {npool * B_CLOUDS * N_POINTS * 12 / 1e6:.0f} MB"
                                   f"{' (> 256 MB MALL)' if npool * B_CLOUDS * N_POINTS * 12 > 256e6 else ''}, each step's batch (and its betas / pose) copied "
                                   "into the call's input buffers on the call's stream inside the timed region"),

@@ -1,5 +1,5 @@
 """SMPL front door on the HIP skinning kernels: `SMPL` / `SMPLLayer` with the reference's constructor arguments, buffers
-and return type (/root/reference/smplx/smplx/body_models.py:44-478), `VertexJointSelector`
+and return type (smplx/smplx/body_models.py:44-478), `VertexJointSelector`
 (smplx/smplx/vertex_joint_selector.py:28-77), and `smpl_clip_batch` -- the three body evaluations per frame (posed,
 T-pose, zero-pose) that the reference's data loader runs one frame at a time on the CPU
 (utils/dataloader.py:186-246), done for all frames of a batch in three batched launches on the GPU, returned under the

@@ -1,4 +1,4 @@
-// Temporal attention of the refinement rounds (/root/reference/modules/mesh_encoder.py:467-476): per clip,
+// Temporal attention of the refinement rounds (modules/mesh_encoder.py:467-476): per clip,
 //   q, k, v = chunk(temporal_qkv(last_feat), 3)            each (T, Vg*C), flattened over the garment vertices
 //   att = softmax(q k^T / sqrt(T))                          (T, T)
 //   out = att v                                             (T, Vg*C)

@@ -1,5 +1,5 @@
 // Cell-bucketed ball query for gfx950 -- the "LDS-bucketed neighbour search" form of ball_query_kernel_fast
-// (/root/reference/modules/pointnet2/pointnet2/src/ball_query_gpu.cu:9-67) for large clouds whose balls are small
+// (modules/pointnet2/pointnet2/src/ball_query_gpu.cu:9-67) for large clouds whose balls are small
 // compared with the cloud (BASELINE configs 2 and 5: a radius-0.1 ball holds 0.4 % of a unit cloud, so > 99 % of the
 // B*M*N pair tests of the scan are avoidable).  Output is bit-identical to g4d_ball_query_msg_f32 for ANY input: the same
 // distance expression (dist2<FM>, g4d_common.h) decides membership, the cells only choose which points get tested.
@@ -207,7 +207,7 @@ __global__ void __launch_bounds__(256) ball_grid_query_kernel(int n, int m, int 
 }
 
 // ---- three nearest neighbours over the cell grid ------------------------------------------------------------------------------
-// three_nn_kernel_fast (/root/reference/modules/pointnet2/pointnet2/src/interpolate_gpu.cu:9-52) scans all m known points per
+// three_nn_kernel_fast (modules/pointnet2/pointnet2/src/interpolate_gpu.cu:9-52) scans all m known points per
 // unknown point; the 3 nearest of a point on a surface sampled by m points sit within a few sample spacings.  The known points
 // are counting-sorted into the finest grid that fits the cell budget (ball_grid_build_kernel, cell_req <= 0); a lane owns one
 // unknown point and walks the 3 x 3 x 3 cells around its own cell (9 contiguous record ranges), keeping the 3 smallest

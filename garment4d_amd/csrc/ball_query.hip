@@ -1,5 +1,5 @@
 // Ball query for gfx950 -- replaces ball_query_kernel_fast / ball_query_kernel_launcher_fast
-// (/root/reference/modules/pointnet2/pointnet2/src/ball_query_gpu.cu:9-67), single- and multi-scale.
+// (modules/pointnet2/pointnet2/src/ball_query_gpu.cu:9-67), single- and multi-scale.
 //
 // Semantics kept: for query q, hits = ascending k with d2 = dist2<FM>(qx-x, qy-y, qz-z) < r*r
 // (fp32 under the process-wide contraction contract of g4d.h -- nvcc's fused shape by default; r*r rounded once in fp32); out = first `nsample` hits, remaining slots

@@ -1,5 +1,5 @@
 // Furthest point sampling for gfx950 -- replaces furthest_point_sampling_kernel(_launcher)
-// (/root/reference/modules/pointnet2/pointnet2/src/sampling_gpu.cu:93-253).
+// (modules/pointnet2/pointnet2/src/sampling_gpu.cu:93-253).
 //
 // Semantics kept bit-for-bit: idx[0]=0; round j: mind[k] = min(d(k,old), mind[k])
 // with d = dist2<FM>(dx, dy, dz) -- the squared distance under the process-wide contraction contract (g4d.h

@@ -1,4 +1,4 @@
-// Kernels of the garment skinning around the hot path (/root/reference/modules/mesh_encoder.py:337-390):
+// Kernels of the garment skinning around the hot path (modules/mesh_encoder.py:337-390):
 //   knn_blend_weights : inverse-distance blend of the K nearest body vertices' skinning weights (:339-347, :374-382)
 //   spmm_axpy_rows    : one Jacobi smoothing step  W <- W + coeff * (adj . W)  over the garment mesh (:385-390, x100)
 // Both HBM/L2-bound gathers with point-major rows; nothing is repeated/expanded the way the reference does it

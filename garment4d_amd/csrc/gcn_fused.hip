@@ -1,5 +1,5 @@
 // Fused "aggregate, then the next layer's contraction" for the GCN stacks of the refinement loop
-// (/root/reference/modules/mesh_encoder.py:477-481 calling modules/pygcn/layers.py:35-55 four times per round).
+// (modules/mesh_encoder.py:477-481 calling modules/pygcn/layers.py:35-55 four times per round).
 //
 // A GraphConvolution is  h = act(Ahat (X W) + b).  Chained, the aggregation of layer i and the contraction of layer i+1 are
 //     h_i = act(Ahat S_i + b_i)        (SpMM: reads S_i seven times through L2 -- once per neighbour -- writes h_i)

@@ -1,6 +1,6 @@
 // Row-streaming fp32 GEMM for the tall contractions of the refinement model (BASELINE config 4) with K <= 128:
 // Y = act((X . W^T) * scale + shift) over ~10^6 rows -- the qkv projection of the temporal attention (128 -> 384 on frames x Vg rows,
-// /root/reference/modules/mesh_encoder.py:469).
+// modules/mesh_encoder.py:469).
 //
 // The LDS-tiled kernel of mlp.hip stages K in chunks of 32 with ONE chunk of look-ahead: 32 MFMAs (0.4 us) of cover against an HBM
 // round trip of 2+ us, so every chunk of every 64 x 64 tile waits for its data (64-66 TFLOP/s on these shapes).  Here a workgroup

@@ -1,5 +1,5 @@
 // K nearest neighbours (K <= 256) for the garment skinning of the model around the hot path: the reference calls
-// `chamferdist.knn_points(garment_verts, body_verts, K=256 / 64 / 1)` (/root/reference/modules/mesh_encoder.py:321-324;
+// `chamferdist.knn_points(garment_verts, body_verts, K=256 / 64 / 1)` (modules/mesh_encoder.py:321-324;
 // chamferdist is an un-vendored dependency, README.md:26, wrapping pytorch3d's KNN: squared L2 distances, the K
 // smallest per query, sorted ascending).  Defined here as: the K smallest under (distance, index) lexicographic order,
 // distance = ((dx*dx) + dy*dy) + dz*dz in fp32 without fma.  PARITY UNPINNED (the dependency is absent; its tie order

@@ -1,5 +1,5 @@
 // SMPL linear blend skinning for gfx950 -- the reference runs this as ~40 small torch ops per call, on the CPU,
-// batch 1, three times per frame inside its DataLoader workers (/root/reference/smplx/smplx/lbs.py:152-248,
+// batch 1, three times per frame inside its DataLoader workers (smplx/smplx/lbs.py:152-248,
 // called from utils/dataloader.py:199-212).  Here it is four kernels over the whole batch of frames:
 //
 //   lbs_shape_kernel   v_shaped = v_template + shapedirs . betas                       (lbs.py:205, 288-309)

@@ -1,10 +1,10 @@
 // Two small HBM-bound kernels of the model around the hot path:
 //   segment_select / segment_take : `PCAGarmentEncoderSeg.calc_segmentation_results`
-//       (/root/reference/modules/mesh_encoder.py:109-125): per frame, the points whose arg-max class is the garment's,
+//       (modules/mesh_encoder.py:109-125): per frame, the points whose arg-max class is the garment's,
 //       in index order, first n_out of them, zero padded.  The reference runs a Python loop over frames with boolean
 //       indexing (one device sync per frame); here one workgroup per frame does an ordered compaction with ballot
 //       prefix sums, then a row gather writes coordinates and point-major features.
-//   vertex_normals : `compute_vnorms` (/root/reference/utils/mesh_utils.py:116-134): unit face normals (norm clamped at
+//   vertex_normals : `compute_vnorms` (utils/mesh_utils.py:116-134): unit face normals (norm clamped at
 //       1e-6) summed per vertex over the incident faces (torch_scatter sum; order = the CSR order given by the caller),
 //       re-normalised with the same clamp.  One thread per (frame, vertex); faces are recomputed per incident vertex
 //       (3x the flops, no (F, nf, 3) intermediate and no atomics -> deterministic).
@@ -131,7 +131,7 @@ extern "C" int g4d_vertex_normals_f32(int frames, int v, const float *verts, con
     return check_launch("g4d_vertex_normals_f32");
 }
 
-// Interpenetration penalty of `calc_interpenetration_loss` (/root/reference/smplx/loss/temporal_loss.py:20-46), forward:
+// Interpenetration penalty of `calc_interpenetration_loss` (smplx/loss/temporal_loss.py:20-46), forward:
 // per garment vertex g with nearest body vertex b (index from the nearest-neighbour search) and its normal n,
 //   pen = relu(-(n . (g - b)))     -- positive when the garment vertex lies behind the body surface.
 namespace g4d {

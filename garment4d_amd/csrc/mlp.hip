@@ -4,11 +4,11 @@
 // never materialised in HBM: a row LOADER builds each 64 x 32 A tile straight into LDS from
 //   DIRECT : point-major activations X[row][k]                                   (hidden layers, FC head)
 //   GROUP  : ball-query neighbourhoods -- [xyz[idx]-centre (3) | feats[idx] (C)]  (QueryAndGroup + cat,
-//            /root/reference/modules/pointnet2/pointnet2/pointnet2_utils.py:242-265; the (B,3+C,P,S) tensor
+//            modules/pointnet2/pointnet2/pointnet2_utils.py:242-265; the (B,3+C,P,S) tensor
 //            the reference writes to HBM and reads back never exists here)
 //   INTERP : [sum_i w_i * known_feats[idx_i] (C2) | skip feats (C1)] with w from the 3-NN distances
 //            (PointnetFPModule.forward, pointnet2_modules.py:139-149)
-//   CSR    : sum_u Ahat[v,u] * X[f,u,:]  (GraphConvolution, /root/reference/modules/pygcn/layers.py:35-55,
+//   CSR    : sum_u Ahat[v,u] * X[f,u,:]  (GraphConvolution, modules/pygcn/layers.py:35-55,
 //            evaluated as (Ahat X) W, algebraically equal to Ahat (X W))
 // and the epilogue fuses the folded BatchNorm affine, ReLU and the max/avg pool over the S samples of a
 // neighbourhood (pointnet2_modules.py:40-53), writing point-major output at a column offset (MSG concat).

@@ -1,5 +1,5 @@
 // gather / group / three_nn / three_interpolate (+ the three scatter-add backward kernels) for gfx950.
-// Replaces /root/reference/modules/pointnet2/pointnet2/src/{sampling_gpu.cu:8-83, group_points_gpu.cu:8-86,
+// Replaces modules/pointnet2/pointnet2/src/{sampling_gpu.cu:8-83, group_points_gpu.cu:8-86,
 // interpolate_gpu.cu:9-161}.  All HBM/L2-bound copies or scans: coalesced along the point axis, the index
 // row is read ONCE per thread and reused for a chunk of channels (the reference re-reads it per channel),
 // 64-bit offsets (the reference's int32 offsets wrap at 2^31 elements).

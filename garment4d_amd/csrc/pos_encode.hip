@@ -1,4 +1,4 @@
-// Positional encoders of the refinement loop (/root/reference/modules/mesh_encoder.py:452-464): per garment vertex q,
+// Positional encoders of the refinement loop (modules/mesh_encoder.py:452-464): per garment vertex q,
 // QueryAndGroup(radius, nsample, use_xyz=True) rows [x_j - q ; f_j] -> Linear(3+C, 32) -> ReLU -> Linear(32, 32) -> max
 // over the nsample rows.  18 such encoders run per forward over Vg * nsample rows each (31 M rows at Vg = 4096, 240
 // frames), with 6- to 387-wide inputs and 32-wide layers -- far too narrow for the LDS-staged stack kernel to pay off.

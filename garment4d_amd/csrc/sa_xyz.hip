@@ -1,5 +1,5 @@
 // Set-abstraction stack over xyz-only neighbourhoods: QueryAndGroup(use_xyz=True, features=None) -> SharedMLP [3, C1, C2, C3] -> pool
-// (/root/reference/modules/pointnet2/pointnet2/pointnet2_modules.py:40-53 with pointnet2_utils.py:242-265; the first level of
+// (modules/pointnet2/pointnet2/pointnet2_modules.py:40-53 with pointnet2_utils.py:242-265; the first level of
 // Pointnet2MSGSEG, pointnet2encoder.py:41-53: [3,16,16,32] over 16 samples and [3,32,32,64] over 32 samples of 1024 centres).
 //
 // The generic register-chain kernel (mlp_chain.hip) treats this like any stack: 32 rows per wave, every wave streams the weights from

@@ -1,4 +1,4 @@
-// three_nn with exact spatial pruning for the last feature-propagation level (/root/reference/modules/pointnet2/pointnet2/src/
+// three_nn with exact spatial pruning for the last feature-propagation level (modules/pointnet2/pointnet2/src/
 // interpolate_gpu.cu:9-74: for every unknown point the three smallest squared distances over ALL m known points, earlier index first
 // among equal distances).  Round 5.
 //

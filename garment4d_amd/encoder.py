@@ -1,5 +1,5 @@
 """PointNet++ MSG segmentation encoder with the layer specification, attribute names and state-dict keys of
-the reference's `Pointnet2MSGSEG` (/root/reference/modules/pointnet2encoder.py:18-145): 3 SA-MSG levels
+the reference's `Pointnet2MSGSEG` (modules/pointnet2encoder.py:18-145): 3 SA-MSG levels
 (1024/256/64 centroids), optional global SA, 3 FP levels and a Conv1d head.  This is the network BASELINE
 config 2 quotes the metric on (`input_channels=0, global_feat=False`, as instantiated at
 modules/mesh_encoder.py:49).

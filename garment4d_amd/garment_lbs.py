@@ -1,5 +1,5 @@
 """Garment skinning by KNN-interpolated body weights -- the immediate caller of the LBS hot path
-(`PCALBSGarmentUseSegEncoderSeg.lbs_garment_interpolation`, /root/reference/modules/mesh_encoder.py:312-410).
+(`PCALBSGarmentUseSegEncoderSeg.lbs_garment_interpolation`, modules/mesh_encoder.py:312-410).
 
 Same inputs / outputs as the reference method; `body_model.parents` and `self.adj_old` (the un-normalised,
 symmetrised garment-mesh adjacency, :299-303) are passed explicitly because this function is not a method of the model.

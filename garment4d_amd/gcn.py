@@ -1,6 +1,6 @@
 """Graph convolution layer with the reference's class name, parameters and forward signature
-(/root/reference/modules/pygcn/layers.py:9-61) plus the two adjacency helpers the model uses
-(/root/reference/modules/pygcn/utils.py:56-63 normalize, :73-80 sparse_mx_to_torch_sparse_tensor; adjacency
+(modules/pygcn/layers.py:9-61) plus the two adjacency helpers the model uses
+(modules/pygcn/utils.py:56-63 normalize, :73-80 sparse_mx_to_torch_sparse_tensor; adjacency
 construction as in modules/mesh_encoder.py:288-307).
 
 forward(input, adj):  out = adj @ (input @ W) + b  -- the reference's order, two HIP kernels per layer: the dense

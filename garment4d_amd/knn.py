@@ -1,6 +1,6 @@
 """`knn_points` with the call shape the reference uses (chamferdist / pytorch3d: `knn_points(p1, p2, K=1)` ->
 object with `.dists` (B,P1,K) squared distances ascending and `.idx` (B,P1,K) int64), on the HIP kernel of csrc/knn.hip.
-Used by the garment skinning around the hot path (/root/reference/modules/mesh_encoder.py:321-324)."""
+Used by the garment skinning around the hot path (modules/mesh_encoder.py:321-324)."""
 from collections import namedtuple
 
 import torch

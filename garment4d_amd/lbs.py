@@ -1,5 +1,5 @@
 """SMPL linear blend skinning with the reference's function names and signatures
-(/root/reference/smplx/smplx/lbs.py: lbs :152, vertices2joints :251, vertices2jointsB :270, blend_shapes :288,
+(smplx/smplx/lbs.py: lbs :152, vertices2joints :251, vertices2jointsB :270, blend_shapes :288,
 batch_rodrigues :312, batch_rigid_transform :362), computed by the HIP kernels of csrc/lbs.hip through the C ABI.
 
 The reference evaluates these on the CPU, batch 1, three times per frame inside DataLoader workers

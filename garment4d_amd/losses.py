@@ -1,5 +1,5 @@
 """Evaluation-side helpers that share the kernels of the hot path, forward only:
-`calc_interpenetration_loss` (/root/reference/smplx/loss/temporal_loss.py:20-46) = vertex normals + nearest body vertex +
+`calc_interpenetration_loss` (smplx/loss/temporal_loss.py:20-46) = vertex normals + nearest body vertex +
 penalty, each on a HIP kernel.  The nearest vertex comes from the three-nearest-neighbour kernel of the feature-propagation
 layers (ties -> lowest index, like knn_points here), not from a K=1 top-K search."""
 import numpy as np

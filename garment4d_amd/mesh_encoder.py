@@ -1,5 +1,5 @@
 """The model around the hot path, wired on the HIP kernels: `PCAGarmentEncoderSeg` and `PCALBSGarmentUseSegEncoderSeg`
-(/root/reference/modules/mesh_encoder.py:43-169, 172-487) with the reference's sub-module names, so a reference
+(modules/mesh_encoder.py:43-169, 172-487) with the reference's sub-module names, so a reference
 checkpoint's `state_dict` loads by key:
 
     PCA_garment_encoder.pointnet.{SA_modules,FP_modules,FC_layer}...   Pointnet2MSGSEG(input_channels=0, global_feat=False)

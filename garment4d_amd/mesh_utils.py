@@ -1,4 +1,4 @@
-"""Mesh helpers of the model around the hot path, same names and argument meaning as /root/reference/utils/mesh_utils.py
+"""Mesh helpers of the model around the hot path, same names and argument meaning as utils/mesh_utils.py
 (readOBJ :8-35, calc_body_mesh_info :83-99, compute_fnorms :116-126, compute_vnorms :128-134) and `quads2tris`
 (modules/mesh_encoder.py:24-31).  The vertex -> incident-face table comes from the face list itself (the reference builds
 it with OpenMesh, absent here; only the summation order of the per-vertex normal sum depends on it).  Normals run on the

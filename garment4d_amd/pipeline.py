@@ -20,9 +20,8 @@ The views stay valid until `streams` further calls have been launched (the slot 
 them.  A partially filled call is launched by flush() (or by result() on one of its steps): the graph then runs on the slot's
 stale tail clouds as well -- wasted work, never wrong results.
 
-hipGraph + streams: the HIP runtime maps streams onto GPU_MAX_HW_QUEUES hardware queues (default 4).  With more streams than queues
-the calls serialise; set GPU_MAX_HW_QUEUES >= `streams` in the environment BEFORE the runtime initialises (i.e. before `import
-torch`), as bench.py does.  `streams` <= 4 needs nothing.
+hipGraph + streams: the HIP runtime maps streams onto the hardware queues the environment allows (GPU_MAX_HW_QUEUES).  Streams
+beyond that share queues: the calls still run, with less overlap between them.
 """
 import ctypes
 

@@ -1,7 +1,7 @@
 """Drop-in for the reference's compiled extension module `pointnet2_cuda`.
 
 Same nine entry points, argument order and in-place output convention as
-/root/reference/modules/pointnet2/pointnet2/src/pointnet2_api.cpp:10-24 (C++ wrappers in
+modules/pointnet2/pointnet2/src/pointnet2_api.cpp:10-24 (C++ wrappers in
 src/sampling.cpp:11-46, ball_query.cpp:14-25, group_points.cpp, interpolate.cpp); each one forwards raw
 device pointers and the current torch stream to the C ABI of libg4d_hip.so (include/g4d.h).
 

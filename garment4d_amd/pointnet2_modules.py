@@ -1,5 +1,5 @@
 """PointnetSAModuleMSG / PointnetSAModule / PointnetFPModule with the reference's constructor signatures,
-forward contracts and state-dict keys (/root/reference/modules/pointnet2/pointnet2/pointnet2_modules.py).
+forward contracts and state-dict keys (modules/pointnet2/pointnet2/pointnet2_modules.py).
 
 forward() has two routes behind the reference's one signature:
 

@@ -1,5 +1,5 @@
 """Operator layer with the reference's names and call signatures
-(/root/reference/modules/pointnet2/pointnet2/pointnet2_utils.py): furthest_point_sample,
+(modules/pointnet2/pointnet2/pointnet2_utils.py): furthest_point_sample,
 gather_operation, three_nn, three_interpolate, grouping_operation, ball_query, QueryAndGroup, GroupAll.
 
 Each op allocates and pre-initialises its outputs the way the reference's Function.forward does

@@ -1,5 +1,5 @@
 """SharedMLP / Conv1d / Conv2d / FC / BatchNorm containers with the reference's constructor signatures and
-STATE-DICT KEYS (/root/reference/modules/pointnet2/pointnet2/pytorch_utils.py): e.g.
+STATE-DICT KEYS (modules/pointnet2/pointnet2/pytorch_utils.py): e.g.
 `layer0.conv.weight (Cout,Cin,1,1)`, `layer0.bn.bn.{weight,bias,running_mean,running_var,num_batches_tracked}`,
 so reference checkpoints load unchanged.  These containers are the trainable (un-fused) path; eval-mode
 inference goes through the fused HIP kernels (garment4d_amd/fused.py), which read these modules' tensors -- the SA / FP

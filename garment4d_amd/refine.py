@@ -1,5 +1,5 @@
 """The temporal garment refinement loop around the hot path -- `PCALBSGarmentUseSegEncoderSeg.forward`'s
-ITERATION rounds (/root/reference/modules/mesh_encoder.py:445-486) with the reference's sub-module names
+ITERATION rounds (modules/mesh_encoder.py:445-486) with the reference's sub-module names
 (`body_positional_encoding{0,1,2}`, `garment_positional_encoding{0,1,2}`, `temporal_qkv_{1,2}`,
 `lbs_graph_regress{1,2,3}`) so that the corresponding slices of a reference checkpoint load by key.
 

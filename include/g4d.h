@@ -14,7 +14,7 @@
  *   - all tensors are contiguous; fp32 data, int32 indices (as the reference: §2a).
  *
  * Each legacy entry point replaces one `*_kernel_launcher*` of the reference
- * (/root/reference/modules/pointnet2/pointnet2/src/, cited per function) -- the raw-pointer seam
+ * (modules/pointnet2/pointnet2/src/, cited per function) -- the raw-pointer seam
  * that the reference's pybind wrappers (src/pointnet2_api.cpp:10-24) already call.
  */
 #ifndef G4D_H
@@ -604,7 +604,7 @@ int g4d_lbs_one_f32(int b, int v, int j, int nb, int pose2rot, const float *beta
                     g4d_stream_t stream);
 
 /* lbs() on the matrix pipe (round 5; csrc/lbs.hip lbs_frame_kernel + lbs_mfma_kernel), same constants and outputs as g4d_lbs_one_f32
- * (replaces /root/reference/smplx/smplx/lbs.py:152-248 for a batch of frames).  Launch 1, one wave per frame, ONCE per frame: Rodrigues, joints
+ * (replaces smplx/smplx/lbs.py:152-248 for a batch of frames).  Launch 1, one wave per frame, ONCE per frame: Rodrigues, joints
  * from betas, kinematic chain -> A_out, posed_joints and the B operands of the two GEMMs (fragment order) in `ws`.  Launch 2, a workgroup per
  * 32 vertices: their blend rows (NC x 96 floats, 86 KB) in LDS, read from HBM once per launch; per (16-frame tile, 16-vertex half)
  * v_posed^T and T^T = (W . A)^T as fp32 MFMA tiles (vertices x frames), so a lane ends with the posed vertex and the full 3x4 transform of the

@@ -6,7 +6,7 @@
  * as the checker / the timed CPU baseline.
  *
  * Every function follows one reference kernel line by line (file:line given per function,
- * relative to /root/reference/modules/pointnet2/pointnet2/src/).  Arithmetic is IEEE fp32.  The one
+ * relative to modules/pointnet2/pointnet2/src/).  Arithmetic is IEEE fp32.  The one
  * expression whose rounding decides INDICES -- the squared distance of FPS, ball query and three_nn,
  *     d = (x2-x1)*(x2-x1) + (y2-y1)*(y2-y1) + (z2-z1)*(z2-z1)      sampling_gpu.cu:136, ball_query_gpu.cu:30,
  *                                                                  interpolate_gpu.cu:33

@@ -1,9 +1,9 @@
 """numpy/scipy fp32 restatement of the reference's GCN layer and adjacency helpers.
 
 TEST INFRASTRUCTURE ONLY (see oracle/__init__.py).  Follows
-/root/reference/modules/pygcn/layers.py:35-55 (GraphConvolution.forward),
-/root/reference/modules/pygcn/utils.py:56-63 (normalize) and the adjacency construction of
-/root/reference/modules/mesh_encoder.py:288-307.  Pinned by tests/golden/gcn_*.npz, produced
+modules/pygcn/layers.py:35-55 (GraphConvolution.forward),
+modules/pygcn/utils.py:56-63 (normalize) and the adjacency construction of
+modules/mesh_encoder.py:288-307.  Pinned by tests/golden/gcn_*.npz, produced
 with the reference's own GraphConvolution imported in the build container.
 """
 import numpy as np

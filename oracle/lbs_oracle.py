@@ -1,6 +1,6 @@
 """numpy fp32 restatement of the reference's SMPL linear blend skinning.
 
-TEST INFRASTRUCTURE ONLY (see oracle/__init__.py).  Follows /root/reference/smplx/smplx/lbs.py
+TEST INFRASTRUCTURE ONLY (see oracle/__init__.py).  Follows smplx/smplx/lbs.py
 function by function; pinned against the reference's own `lbs`, `batch_rigid_transform`,
 `batch_rodrigues`, `vertices2jointsB` imported in the build container (tests/golden/make_golden.py
 -> tests/golden/lbs_*.npz).

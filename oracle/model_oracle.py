@@ -1,5 +1,5 @@
 """TEST INFRASTRUCTURE ONLY.  numpy restatement of the model around the hot path -- `PCAGarmentEncoderSeg.forward`
-(/root/reference/modules/mesh_encoder.py:127-169), `compute_vnorms` (utils/mesh_utils.py:116-134) and
+(modules/mesh_encoder.py:127-169), `compute_vnorms` (utils/mesh_utils.py:116-134) and
 `PCALBSGarmentUseSegEncoderSeg.forward` (:412-487) -- composed from the pinned pointnet2 / lbs / gcn oracles.
 Pinned in parts: compute_vnorms and the refinement loop + garment skinning (through refine_oracle) against the reference's own
 utils/mesh_utils.py and modules/mesh_encoder.py (tests/golden/refine.npz, make_golden_refine.py); the SA / FP / head stack against

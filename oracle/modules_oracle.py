@@ -1,7 +1,7 @@
 """numpy fp32 restatement of the reference's L1/L2 PointNet++ Python layer.
 
 TEST INFRASTRUCTURE ONLY (see oracle/__init__.py).  Follows
-/root/reference/modules/pointnet2/pointnet2/pointnet2_utils.py:232-291 (QueryAndGroup, GroupAll),
+modules/pointnet2/pointnet2/pointnet2_utils.py:232-291 (QueryAndGroup, GroupAll),
 pointnet2_modules.py:19-55,116-156 (SA / FP forward) and pytorch_utils.py:5-32 (SharedMLP =
 [1x1 conv (bias-free when bn) -> BatchNorm -> ReLU] per layer), on top of the C oracle kernels.
 Pinned by tests/golden/modules_*.npz (reference's own modules run on the oracle kernels).
@@ -120,7 +120,7 @@ def fp_module(unknown, known, unknow_feats, known_feats, sd, training=False):
     return shared_mlp(x[..., None].astype(F32), sd, prefix="mlp.", training=training)[..., 0]
 
 
-# /root/reference/modules/pointnet2encoder.py:41-96 -- (npoint, radii, nsamples) of the three SA-MSG levels
+# modules/pointnet2encoder.py:41-96 -- (npoint, radii, nsamples) of the three SA-MSG levels
 ENCODER_SA_SPEC = [(1024, [0.05, 0.1], [16, 32]), (256, [0.1, 0.2], [16, 32]), (64, [0.2, 0.4], [32, 64])]
 
 

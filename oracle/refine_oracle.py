@@ -1,5 +1,5 @@
 """numpy restatement of the garment-skinning / refinement code AROUND the hot path
-(/root/reference/modules/mesh_encoder.py:312-487).  TEST INFRASTRUCTURE ONLY.
+(modules/mesh_encoder.py:312-487).  TEST INFRASTRUCTURE ONLY.
 
 PINNED (round 5) against the reference's OWN modules/mesh_encoder.py, run in the build container with its absent third-party imports
 stubbed (tests/golden/make_golden_refine.py -> tests/golden/refine.npz; tests/test_oracle_golden.py checks lbs_garment_interpolation at
@@ -72,7 +72,7 @@ def lbs_garment_interpolation(garment_t, Tpose_vertices, Tpose_root_joints, zero
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# The refinement loop of PCALBSGarmentUseSegEncoderSeg.forward (/root/reference/modules/mesh_encoder.py:445-486),
+# The refinement loop of PCALBSGarmentUseSegEncoderSeg.forward (modules/mesh_encoder.py:445-486),
 # restated with numpy on top of the pinned pointnet2 / gcn oracles; pinned as a whole by tests/golden/refine.npz (the reference's own
 # forward() run with a stub garment encoder: tests/golden/make_golden_refine.py).
 def _linear(x, w, b=None):

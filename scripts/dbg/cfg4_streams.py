@@ -1,7 +1,6 @@
 """Config 4 (8 clips x 30 frames) as K concurrent part-forwards on K streams (clips split evenly): does overlapping one part's sampling / searches with
 another's shared MLPs help the whole forward?   python scripts/dbg/cfg4_streams.py [K=2]"""
 import os, sys, time, types
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "32")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np, torch
 from garment4d_amd import synthetic as syn

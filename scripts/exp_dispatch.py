@@ -1,7 +1,6 @@
 """How much of a small launch's cost in the 16-stream regime is dispatch?  K dependent launches of a tiny kernel per stream (hipGraph), 1..32 streams:
 us per launch = wall / (streams * K).  python scripts/exp_dispatch.py"""
 import os, sys, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "32")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from garment4d_amd import _lib

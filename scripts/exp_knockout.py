@@ -7,7 +7,6 @@ G4D_KNOCK_TRACE=1 prints the C-ABI calls of one step."""
 import fnmatch, os, runpy, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "32")
 import torch  # noqa: F401
 from garment4d_amd import _lib
 

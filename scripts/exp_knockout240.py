@@ -5,7 +5,6 @@ flight, the executor's regime, no host work in between) and timed per call; then
 behind the other calls' launches (dependent rounds on a few waves); one at its full duration is issue-slot-bound like its neighbours.
     python scripts/exp_knockout240.py [B=240] [precision] [NS=8]"""
 import os, sys, gc, ctypes
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "32")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from garment4d_amd import synthetic as syn, lbs as G, _lib

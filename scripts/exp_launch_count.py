@@ -2,7 +2,6 @@
 (g4d_linear_f32, rows x 64 -> 64); the same total rows are processed as K launches of R rows or K/2 launches of 2R rows.
 python scripts/exp_launch_count.py"""
 import os, sys, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "32")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from garment4d_amd import fused

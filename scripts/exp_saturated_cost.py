@@ -2,7 +2,6 @@
 by copies of itself) next to its isolated duration.  Sum of the saturated costs ~ the step time the 16-batch bench can reach.
 python scripts/exp_saturated_cost.py"""
 import os, sys, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "32")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 from garment4d_amd import fused, _lib, synthetic as syn, lbs as G

@@ -1,6 +1,5 @@
 """What bounds the 16-batch throughput?  Replays the cfg2 step graphs with pieces removed.  python scripts/exp_throughput.py"""
 import os, sys, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "32")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 from garment4d_amd import fused, synthetic as syn, lbs as G

@@ -2,7 +2,7 @@
 """Generate tests/golden/*.npz by running the REFERENCE's own Python in the build container.
 
 Run from the repo root:  python tests/golden/make_golden.py
-Needs /root/reference (read-only); never runs on the GPU box.  Only DATA is written (inputs,
+Needs a checkout of the reference, named by G4D_REFERENCE_DIR (read-only); needs no GPU.  Only DATA is written (inputs,
 weights, expected outputs) -- no reference source travels.
 
 What is imported from the reference, unmodified:
@@ -23,8 +23,8 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
-REF = "/root/reference"
-OUT = os.environ.get("G4D_GOLDEN_OUT") or os.path.join(ROOT, "tests", "golden")   # (tests/test_golden_repro_cpu.py regenerates into a temp dir)
+REF = os.environ.get("G4D_REFERENCE_DIR") or sys.exit("set G4D_REFERENCE_DIR to a checkout of the reference")
+OUT = os.environ.get("G4D_GOLDEN_OUT") or os.path.join(ROOT, "tests", "golden")   # (G4D_GOLDEN_OUT: regenerate elsewhere, to compare)
 
 from garment4d_amd import synthetic as syn  # noqa: E402
 from oracle import pointnet2_oracle as K  # noqa: E402

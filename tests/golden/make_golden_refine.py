@@ -2,8 +2,8 @@
 """Generate tests/golden/refine.npz by running the REFERENCE's own `modules/mesh_encoder.py` in the build container.
 
 Run from the repo root:  python tests/golden/make_golden_refine.py          (its own process: it installs a synthetic top-level
-`smplx` package, which conflicts with the `smplx` = /root/reference/smplx/smplx of make_golden.py)
-Needs /root/reference (read-only); never runs on the GPU box.  Only DATA is written (expected outputs + input checksums; the inputs
+`smplx` package, which conflicts with the `smplx` = <reference>/smplx/smplx of make_golden.py)
+Needs a checkout of the reference, named by G4D_REFERENCE_DIR (read-only); needs no GPU.  Only DATA is written (expected outputs + input checksums; the inputs
 are regenerated from seeds by garment4d_amd/synthetic.py:refine_golden_case) -- no reference source travels.
 
 What runs unmodified from the reference:
@@ -41,8 +41,8 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
-REF = "/root/reference"
-OUT = os.environ.get("G4D_GOLDEN_OUT") or os.path.join(ROOT, "tests", "golden")   # (tests/test_golden_repro_cpu.py regenerates into a temp dir)
+REF = os.environ.get("G4D_REFERENCE_DIR") or sys.exit("set G4D_REFERENCE_DIR to a checkout of the reference")
+OUT = os.environ.get("G4D_GOLDEN_OUT") or os.path.join(ROOT, "tests", "golden")   # (G4D_GOLDEN_OUT: regenerate elsewhere, to compare)
 
 from garment4d_amd import synthetic as syn  # noqa: E402
 from oracle import pointnet2_oracle as K  # noqa: E402

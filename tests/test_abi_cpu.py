@@ -64,7 +64,7 @@ def test_mlp_argument_block_mirrors_the_header():
 
 def test_shim_has_reference_entry_points():
     from garment4d_amd import pointnet2_cuda as shim
-    # /root/reference/modules/pointnet2/pointnet2/src/pointnet2_api.cpp:10-24
+    # modules/pointnet2/pointnet2/src/pointnet2_api.cpp:10-24
     for name in ["ball_query_wrapper", "group_points_wrapper", "group_points_grad_wrapper", "gather_points_wrapper",
                  "gather_points_grad_wrapper", "furthest_point_sampling_wrapper", "three_nn_wrapper",
                  "three_interpolate_wrapper", "three_interpolate_grad_wrapper"]:

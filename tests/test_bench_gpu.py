@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -11,17 +12,19 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_prints_one_json_line_with_the_contract_keys():
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "8", "--warmup", "1", "--min-seconds", "0.05", "--cpu-frames", "2"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "8", "--warmup", "1", "--cpu-frames", "2"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, lines
     d = json.loads(lines[0])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data",
-              "config", "roofline", "cpu_baseline", "latency_ms_single_stream", "latency_frames_per_s", "latency_ms_one_call", "repeats", "whole_path",
+              "config", "roofline", "cpu_baseline", "latency_ms_single_stream", "latency_frames_per_s", "latency_ms_one_call", "whole_path",
               "roofline_mfma_all", "roofline_fps", "roofline_hbm", "launches"):
         assert k in d, k
     assert d["n_gpus"] == 1 and d["steps"] == 8 and d["warmup"] == 1 and d["higher_is_better"] is True and d["scaling"] == "weak"
+    # --steps is the number of timed steps, and ms_per_step is the timed region over them
+    assert d["config"]["timed_steps"] == 8 and abs(d["ms_per_step"] - d["config"]["timed_seconds"] * 1e3 / 8) < 1e-9
     assert d["unit"] == "frames/s" and d["value"] > 1000 and d["dtype"] == "f32" and d["data"] == "synthetic" and d["vs_baseline"] is None
     assert "workload" in d["config"] and "model" not in d["config"]
     r = d["roofline"]
@@ -56,7 +59,7 @@ def test_bench_gpus_2_launches_two_ranks_by_itself():
     reports TWO ranks (gloo backend: both ranks share the one GPU of this box; the data path has no collective)."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "4", "--warmup", "1",
-                        "--min-seconds", "0.05", "--streams", "4", "--input-pool-mb", "16", "--no-cpu-baseline"],
+                        "--streams", "4", "--input-pool-mb", "16", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     d = _one_json_line(p)
     assert d["n_gpus"] == 2 and d["steps"] == 4 and d["value"] > 1000
@@ -80,3 +83,33 @@ def test_bench_model_frame_sharded_two_ranks_by_itself():
                        capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     d = _one_json_line(p)
     assert d["n_gpus"] == 2 and d["config"]["sharding"] == "frames" and d["config"]["finite"] is True and d["config"]["frames_local"] == 3
+
+
+def test_bench_dump_outputs_are_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: the last timed step's outputs as DIR/<name>.npy (float32), the same as the path run directly on that step's
+    inputs, which the bench draws from its seeded pool (warm-up steps, then one replay of every call, then the timed steps)."""
+    steps, warmup, kco, ns, pool_mb = 3, 1, 2, 2, 16.0
+    out = tmp_path / "dump"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", str(warmup), "--coalesce", str(kco),
+                        "--streams", str(ns), "--input-pool-mb", str(pool_mb), "--no-cpu-baseline", "--no-dropin", "--dump-outputs", str(out)],
+                       capture_output=True, text=True, timeout=600, cwd=ROOT)
+    d = _one_json_line(p)
+    assert d["steps"] == steps and d["config"]["timed_steps"] == steps
+    assert sorted(os.listdir(out)) == ["joints.npy", "sem_logits.npy", "verts.npy"]
+    got = {n: np.load(out / f"{n}.npy") for n in ("sem_logits", "verts", "joints")}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in got.values())
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    from garment4d_amd import lbs as G
+    dev = torch.device("cuda", 0)
+    model, lbs_in, pool, pose_pool = bench.build_workload(dev, True, pool_mb)
+    k = warmup + kco * ns + steps - 1
+    smpl = lbs_in[1]
+    betas, pose = pose_pool[k % len(pose_pool)]
+    with torch.no_grad():
+        logits = model.forward_fused(pool[k % pool.shape[0]].contiguous())[1]
+        v, j = G.lbs(betas, pose, smpl["v_template"], smpl["shapedirs"], smpl["posedirs"], smpl["J_regressor"], smpl["parents"], smpl["lbs_weights"])
+    assert got["sem_logits"].shape == (8, 8192, logits.shape[-1]) and got["verts"].shape == tuple(v.shape) and got["joints"].shape == tuple(j.shape)
+    for name, want in (("sem_logits", logits), ("verts", v), ("joints", j)):
+        np.testing.assert_allclose(got[name], want.float().cpu().numpy(), rtol=1e-5, atol=1e-5, err_msg=name)
