@@ -174,3 +174,52 @@ def lbs_garment_interpolation(pred_template_garment_v, Tpose_vertices, Tpose_roo
         nn_W = smooth_weights(nn_W, adj_old, 0.1, 100)                             # :385-390
     verts = L.skin(nn_W, A, inv_template_garment_v, group=T if shared_W else 1)   # :393, :406-408
     return verts.reshape(B, T, -1, 3), nn1, inv_template_garment_v.reshape(B, T, -1, 3)
+
+
+def _inv_template_pose_mats(F_, device):
+    """The fixed inverse template pose of :543-546 (root -pi/2 about x, hips +-0.15 about y) as (F,24,3,3) rotation matrices."""
+    inv_pose = torch.zeros((1, 24, 3), dtype=torch.float32, device=device)
+    inv_pose[:, 0, 0] = -np.pi / 2
+    inv_pose[:, 1, 1] = 0.15
+    inv_pose[:, 2, 1] = -0.15
+    return L.batch_rodrigues(inv_pose.reshape(-1, 3)).reshape(1, 24, 3, 3).expand(F_, 24, 3, 3).contiguous()
+
+
+def lbs_garment_MGN(pred_template_garment_v, Tpose_vertices, Tpose_root_joints, zeropose_vertices, parents, gt_pose, T_J_regressor,
+                    T_lbs_weights, K=1):
+    """`PCALBSGarmentUseSegEncoderSegMGN.lbs_garment_MGN` (modules/mesh_encoder.py:529-585).  pred_template_garment_v (B,T,Vg,3);
+    Tpose_vertices (B,[1,]V,3); Tpose_root_joints (B,[1,]3); zeropose_vertices (B,T,V,3); gt_pose (B,T,72); T_J_regressor (B,T,J,V);
+    T_lbs_weights (B,T,V,J).  Returns (posed (B,T,Vg,3), nearest body vertex KNN with dists / idx (B*T,Vg,1), stage 1 = the garment
+    un-posed by the inverse template pose (B,T,Vg,3)).
+    The joints and the two sets of joint transforms come from the lbs helpers (inv_A: per-frame regressor on the clip's T-pose, :548-550;
+    A: per-frame regressor on the zero-pose vertices, :562-564); the K = 1 search and both blends at the nearest vertex are ONE launch
+    (g4d_mgn_skin_f32): the (B*T, V, 4, 4) blends of :553 / :568 never exist."""
+    assert pred_template_garment_v.dim() == 4 and pred_template_garment_v.shape[-1] == 3
+    assert gt_pose.dim() == 3 and gt_pose.shape[2] == 72
+    assert K == 1
+    B, T = gt_pose.shape[0], gt_pose.shape[1]
+    F_ = B * T
+    dev = gt_pose.device
+    Vg = pred_template_garment_v.shape[2]
+    J = T_J_regressor.shape[2]
+    body = L._f32(Tpose_vertices, "Tpose_vertices").reshape(B, -1, 3)
+    V = body.shape[1]
+    garment = L._f32(pred_template_garment_v, "pred_template_garment_v").reshape(F_, Vg, 3)
+    root = L._f32(Tpose_root_joints, "Tpose_root_joints").reshape(B, 3)
+    Jreg = L._f32(T_J_regressor, "T_J_regressor").reshape(F_, J, V)
+    W = L._f32(T_lbs_weights, "T_lbs_weights").reshape(F_, V, J)
+    if not (tuple(pred_template_garment_v.shape[:2]) == (B, T) and tuple(T_lbs_weights.shape) == (B, T, V, J)
+            and tuple(T_J_regressor.shape) == (B, T, J, V) and zeropose_vertices.numel() == F_ * V * 3):
+        raise RuntimeError("lbs_garment_MGN: inputs disagree on (B, T, Vg, V, J)")
+    gt_pose_mat = L.batch_rodrigues(gt_pose.reshape(-1, 3).contiguous()).reshape(F_, 24, 3, 3)
+    body_f = body.reshape(B, 1, V, 3).expand(B, T, V, 3).reshape(F_, V, 3)       # new_Tpose_vertices (:540)
+    _, inv_A = L.batch_rigid_transform(_inv_template_pose_mats(F_, dev), L.vertices2jointsB(Jreg, body_f), parents)
+    Jz = L.vertices2jointsB(Jreg, zeropose_vertices.reshape(F_, V, 3))
+    _, A = L.batch_rigid_transform(gt_pose_mat, Jz, parents)
+    idx = torch.empty((F_, Vg, 1), dtype=torch.int32, device=dev)
+    dists = torch.empty((F_, Vg, 1), dtype=torch.float32, device=dev)
+    stage1 = torch.empty((F_, Vg, 3), dtype=torch.float32, device=dev)
+    posed = torch.empty((F_, Vg, 3), dtype=torch.float32, device=dev)
+    _lib.call("g4d_mgn_skin_f32", B, T, Vg, V, J, garment.data_ptr(), root.data_ptr(), body.data_ptr(), W.data_ptr(), inv_A.data_ptr(),
+              A.data_ptr(), idx.data_ptr(), dists.data_ptr(), stage1.data_ptr(), posed.data_ptr(), _lib.stream_ptr())
+    return posed.reshape(B, T, Vg, 3), KNN(dists=dists, idx=idx.long(), knn=None), stage1.reshape(B, T, Vg, 3)

@@ -1,12 +1,13 @@
-"""The model around the hot path, wired on the HIP kernels: `PCAGarmentEncoderSeg` and `PCALBSGarmentUseSegEncoderSeg`
-(modules/mesh_encoder.py:43-169, 172-487) with the reference's sub-module names, so a reference
-checkpoint's `state_dict` loads by key:
+"""The model around the hot path, wired on the HIP kernels: `PCAGarmentEncoderSeg`, `PCALBSGarmentUseSegEncoderSeg` and its MGN
+variant `PCALBSGarmentUseSegEncoderSegMGN` (modules/mesh_encoder.py:43-169, 172-487, 489-614) with the reference's sub-module names,
+so a reference checkpoint's `state_dict` loads by key:
 
     PCA_garment_encoder.pointnet.{SA_modules,FP_modules,FC_layer}...   Pointnet2MSGSEG(input_channels=0, global_feat=False)
     PCA_garment_encoder.GarmentEncoder.{0,1}...                        two MSG set-abstraction levels on the garment points
     PCA_garment_encoder.GarmentSummarize...                            group-all SA  (384+3 -> 512 -> 512)
     PCA_garment_encoder.PCAEncoder.{0,1,3,4,6}...                      Conv1d/BN head 512 -> 128 -> 64 -> 64
     {body,garment}_positional_encoding{0,1,2}, temporal_qkv_{1,2}, lbs_graph_regress{1,2,3}     (refine.GarmentRefinementHead)
+    displacement_encoder.{0,2,4}                                       MGN variant: Linear 512 -> 1024 -> 2048 -> 3 Vg
 
 Inference only.  What the constructor needs from disk in the reference (the PCA basis pickle
 and the garment template OBJ, both part of the CLOTH3D-derived data set that is not available here) can be given either
@@ -26,7 +27,7 @@ from . import fused
 from . import gcn
 from . import mesh_utils
 from .encoder import Pointnet2MSGSEG
-from .garment_lbs import lbs_garment_interpolation
+from .garment_lbs import lbs_garment_interpolation, lbs_garment_MGN
 from .pointnet2_modules import PointnetSAModule, PointnetSAModuleMSG
 from .refine import GarmentRefinementHead
 
@@ -261,3 +262,116 @@ class PCALBSGarmentUseSegEncoderSeg(GarmentRefinementHead):
             frame_ids=fid_t, clip_range=(ids[0] // T, ids[-1] // T))
         return out
 
+
+
+class PCALBSGarmentUseSegEncoderSegMGN(nn.Module):
+    """The MGN baseline (modules/mesh_encoder.py:489-614; train_temporal.py builds it for `--MGN 1`): the PCA garment encoder, a per-frame
+    displacement MLP on the garment summary, and nearest-body-vertex skinning (`lbs_garment_MGN`, one HIP launch for the search and both
+    blends).  No refinement head.  Constructor: the reference's (cfg, args), or garment_name / pca_dim / pca / template as in
+    PCALBSGarmentUseSegEncoderSeg."""
+
+    def __init__(self, cfg=None, args=None, *, garment_name=None, pca_dim=None, pca=None, template=None):
+        super().__init__()
+        self.cfg, self.args = cfg, args
+        self.PCA_garment_encoder = PCAGarmentEncoderSeg(cfg, args, garment_name=garment_name, pca_dim=pca_dim, pca=pca, template=template,
+                                                        only_seg=False)
+        self.remesh_cylinder_f = self.PCA_garment_encoder.remesh_cylinder_f
+        nv = self.PCA_garment_encoder.garment_v_num
+        self.adj_old = gcn.adjacency_old_from_faces(self.remesh_cylinder_f, nv)            # :500-514
+        self.adj = gcn.sparse_mx_to_torch_sparse_tensor(gcn.adjacency_from_faces(self.remesh_cylinder_f, nv))   # :515-516
+        self.vf_fid = None
+        self.vf_vid = None
+        self.displacement_encoder = nn.Sequential(nn.Linear(512, 1024), nn.ReLU(), nn.Linear(1024, 2048), nn.ReLU(), nn.Linear(2048, nv * 3))
+
+    def lbs_garment_MGN(self, pred_template_garment_v, Tpose_vertices, Tpose_root_joints, zeropose_vertices, body_model, gt_pose, T_J_regressor,
+                        T_lbs_weights, K=3):
+        return lbs_garment_MGN(pred_template_garment_v, Tpose_vertices, Tpose_root_joints, zeropose_vertices, body_model.parents, gt_pose,
+                               T_J_regressor, T_lbs_weights, K=K)
+
+    def _displacement_layers(self):
+        """The three Linear layers as packed HIP layers (bias as the shift), rebuilt when a parameter changes."""
+        mods = [m for m in self.displacement_encoder if isinstance(m, nn.Linear)]
+        key = tuple((p.data_ptr(), _lib.ver(p), str(p.device)) for p in self.displacement_encoder.parameters())
+        hit = getattr(self, "_g4d_disp", None)
+        if hit is None or hit[0] != key:
+            with torch.no_grad():
+                layers = [fused.PackedLayer(m.weight.detach().float(), torch.ones(m.out_features, device=m.weight.device), m.bias.detach().float(),
+                                            relu=i < len(mods) - 1) for i, m in enumerate(mods)]
+            hit = self._g4d_disp = (key, layers)
+        return hit[1]
+
+    def displacements(self, garment_summary):
+        """(F, 512) garment summary -> (F, Vg, 3) displacements: the MLP on the HIP linear kernels, * 0.05, NaN -> 0 (:597-601)."""
+        h = garment_summary.reshape(-1, 512).float().contiguous()
+        for layer in self._displacement_layers():
+            h = fused.linear(h, layer)
+        d = h.reshape(h.shape[0], -1, 3) * 0.05
+        return d.masked_fill_(torch.isnan(d), 0.0)
+
+    def _lap_adj_on(self, dev):
+        if getattr(self, "_lap_adj", None) is None or self._lap_adj.device != dev:     # constant of the mesh: built once
+            import scipy.sparse as sp
+            lap_adj = sp.eye(self.adj_old.shape[0]) - gcn.normalize(self.adj_old)
+            self._lap_adj = gcn.sparse_mx_to_torch_sparse_tensor(lap_adj).to(dev)
+        return self._lap_adj
+
+    def forward(self, x, body_model, batch, *, precision="fp32"):
+        """x (nbatch, T, N, 3); body_model needs `.parents`; batch holds the reference's keys (`Tpose_smpl_vertices_torch`,
+        `Tpose_smpl_root_joints_torch`, `zeropose_smpl_vertices_torch`, `pose_torch`, `T_J_regressor`, `T_lbs_weights`) with the same
+        leading (nbatch, T) as x.  precision as in PCALBSGarmentUseSegEncoderSeg.forward (the encoder's MLP operands only)."""
+        assert not torch.is_grad_enabled() and not self.training, "inference only: model.eval() under torch.no_grad()"
+        nbatch, T = x.size(0), x.size(1)
+        dev = x.device
+        with fused.precision(precision):
+            out = self.PCA_garment_encoder(x, body_model, group=False)    # whole clips on this rank: no exchange
+        out["lap_adj"] = self._lap_adj_on(dev)
+        regressed = out["tpose_garment"].reshape(nbatch, 1, -1, 3)
+        t_garment = regressed + self.displacements(out["garment_summary"]).reshape(nbatch, T, -1, 3)         # :602
+        out["lbs_pred_garment_v"], out["lbs_nn"], out["lbs_stage1_pred_garment_v"] = self.lbs_garment_MGN(
+            t_garment, batch["Tpose_smpl_vertices_torch"].to(dev), batch["Tpose_smpl_root_joints_torch"].to(dev),
+            batch["zeropose_smpl_vertices_torch"].to(dev), body_model, batch["pose_torch"].to(dev), batch["T_J_regressor"].to(dev),
+            batch["T_lbs_weights"].to(dev), K=1)
+        out["iter_regressed_lbs_garment_v"] = [out["lbs_pred_garment_v"].reshape(nbatch * T, -1, 3).contiguous()]
+        return out
+
+    def forward_frames(self, x, body_model, batch, *, nbatch, T, frame_ids, group=gdist.WORLD, precision="fp32"):
+        """Frame-sharded forward: this rank holds the frames `frame_ids` (ascending global ids, clip = id // T) of the nbatch x T frames.
+        x (F_local, N, 3); batch: per-FRAME tensors for the local frames (`zeropose_smpl_vertices_torch` (F_local,V,3), `pose_torch`
+        (F_local,72), `T_J_regressor` (F_local,J,V), `T_lbs_weights` (F_local,V,J)) and per-CLIP tensors for all clips
+        (`Tpose_smpl_vertices_torch` (nbatch,V,3), `Tpose_smpl_root_joints_torch` (nbatch,3)).  The one exchange is the encoder's
+        all-reduce MAX of the (nbatch, 512) garment summary; everything after it is per frame.  Same output keys as `forward`, for the
+        local frames (`lbs_pred_garment_v` / `lbs_stage1_pred_garment_v` (F_local,Vg,3), `lbs_nn` with (F_local,Vg,1))."""
+        assert not torch.is_grad_enabled() and not self.training, "inference only: model.eval() under torch.no_grad()"
+        dev = x.device
+        ids = [int(i) for i in frame_ids]
+        assert ids == sorted(ids) and len(ids) == x.shape[0]
+        fid_t = torch.tensor(ids, dtype=torch.long, device=dev)
+        with fused.precision(precision):
+            out = self.PCA_garment_encoder(x, body_model, nbatch=nbatch, T=T, frame_ids=fid_t, group=group)
+        out["lap_adj"] = self._lap_adj_on(dev)
+        regressed = out["tpose_garment"].reshape(nbatch, -1, 3)                  # replicated on every rank (after the all-reduce)
+        disp = self.displacements(out["garment_summary"])                       # (F_local, Vg, 3)
+        Vg = regressed.shape[1]
+        posed = torch.empty((len(ids), Vg, 3), dtype=torch.float32, device=dev)
+        stage1 = torch.empty_like(posed)
+        nn_idx = torch.empty((len(ids), Vg, 1), dtype=torch.long, device=dev)
+        nn_d = torch.empty((len(ids), Vg, 1), dtype=torch.float32, device=dev)
+        lo = 0
+        while lo < len(ids):                                                     # one call per clip segment held by this rank
+            c = ids[lo] // T
+            hi = lo
+            while hi < len(ids) and ids[hi] // T == c:
+                hi += 1
+            seg = slice(lo, hi)
+            p, nn1, s1 = lbs_garment_MGN(
+                (regressed[c:c + 1].unsqueeze(1) + disp[seg].unsqueeze(0)), batch["Tpose_smpl_vertices_torch"][c:c + 1].to(dev),
+                batch["Tpose_smpl_root_joints_torch"][c:c + 1].to(dev), batch["zeropose_smpl_vertices_torch"][seg].to(dev).unsqueeze(0),
+                body_model.parents, batch["pose_torch"][seg].to(dev).unsqueeze(0), batch["T_J_regressor"][seg].to(dev).unsqueeze(0),
+                batch["T_lbs_weights"][seg].to(dev).unsqueeze(0), K=1)
+            posed[seg], stage1[seg], nn_idx[seg], nn_d[seg] = p[0], s1[0], nn1.idx, nn1.dists
+            lo = hi
+        from .knn import KNN
+        out["lbs_pred_garment_v"], out["lbs_stage1_pred_garment_v"] = posed, stage1
+        out["lbs_nn"] = KNN(dists=nn_d, idx=nn_idx, knn=None)
+        out["iter_regressed_lbs_garment_v"] = [posed]
+        return out

@@ -207,3 +207,35 @@ def refine_golden_checksum(case):
     items = [case["tpose_garment"]] + case["garment_v_list"] + case["garment_f_list"] + [v for _, v in sorted(case["batch"].items())]
     items += [v for _, v in sorted(refine_state_dict(seed=case["seed"] + 100).items())]
     return np.array([float(np.asarray(a, dtype=np.float64).sum()) for a in items])
+
+
+def mgn_displacement_state_dict(vg, seed=0):
+    """Seeded weights under the reference's names for the MGN variant's `displacement_encoder` (modules/mesh_encoder.py:518-524:
+    Linear 512 -> 1024 -> 2048 -> 3 vg), drawn like torch's default Linear initialisation (uniform +-1/sqrt(in)).  numpy, fp32."""
+    rng = np.random.default_rng(seed)
+    sd = {}
+    for i, (cin, cout) in zip((0, 2, 4), ((512, 1024), (1024, 2048), (2048, vg * 3))):
+        b = 1.0 / np.sqrt(cin)
+        sd["displacement_encoder.%d.weight" % i] = ((rng.random((cout, cin)) * 2 - 1) * b).astype(F32)
+        sd["displacement_encoder.%d.bias" % i] = ((rng.random(cout) * 2 - 1) * b).astype(F32)
+    return sd
+
+
+def mgn_golden_case(seed=90, nbatch=2, T=3):
+    """The inputs of tests/golden/mgn.npz (written by tests/golden/make_golden_mgn.py, which runs the reference's own MGN variant on them):
+    a 320-vertex body cylinder, a 160-vertex quad-cylinder garment template, per-FRAME skinning weights and joint regressors (the clip's
+    tables with a per-frame perturbation of their non-zero entries, renormalised), per-clip PCA garments, per-frame garment summaries
+    and per-frame displaced garments for lbs_garment_MGN."""
+    sc = garment_scene(nbatch, T, 4, body_rc=(16, 20), garment_rc=(10, 16), seed=seed)
+    rng = np.random.default_rng(seed + 11)
+    gv, gq = sc["template"]
+    Vg = gv.shape[0]
+    batch = dict(sc["batch"])
+    for key, axis in (("T_lbs_weights", -1), ("T_J_regressor", -1)):
+        t = batch[key] * (1 + 0.2 * rng.random(batch[key].shape)).astype(F32)
+        batch[key] = (t / t.sum(axis, keepdims=True)).astype(F32)
+    tpose_garment = (gv[None] + rng.standard_normal((nbatch, Vg, 3)) * 0.004).astype(F32)
+    garment_summary = (rng.random((nbatch, T, 512)) * rng.random((nbatch, T, 512))).astype(F32)
+    pred_template = (tpose_garment[:, None] + rng.standard_normal((nbatch, T, Vg, 3)) * 0.01).astype(F32)
+    return dict(seed=seed, nbatch=nbatch, T=T, Vg=Vg, batch=batch, body=sc["body"], template_verts=gv, template_faces=gq,
+                tpose_garment=tpose_garment, garment_summary=garment_summary, pred_template=pred_template)

@@ -31,7 +31,7 @@ typedef struct ihipStream_t *g4d_stream_t; /* == hipStream_t */
 #define G4D_OK 0
 #define G4D_EINVAL 10001 /* bad argument (negative size, null pointer, unsupported width) */
 
-int g4d_version(void); /* 100 * major + minor: 200 = round 2 (the `boxes` scratch of g4d_ball_query_boxes_f32 grew to 16-point sub-blocks); 205 / 206 = round 5 (entry points added, none changed; 206: g4d_gcn_tile_meta_*, g4d_gcn_agg_linear_meta_f32); 260 = round 6 (added: g4d_mlp_run / g4d_mlp_args, g4d_mlp_chain_group_table_ws_f32, g4d_sa_table_ws_bytes, g4d_sa_table_supported; none changed) */
+int g4d_version(void); /* 100 * major + minor: 200 = round 2 (the `boxes` scratch of g4d_ball_query_boxes_f32 grew to 16-point sub-blocks); 205 / 206 = round 5 (entry points added, none changed; 206: g4d_gcn_tile_meta_*, g4d_gcn_agg_linear_meta_f32); 260 = round 6 (added: g4d_mlp_run / g4d_mlp_args, g4d_mlp_chain_group_table_ws_f32, g4d_sa_table_ws_bytes, g4d_sa_table_supported; none changed); 261 (entry points added, none changed: g4d_mgn_skin_f32) */
 const char *g4d_last_error(void);
 
 /* ---- numerics: how the squared distance of FPS / ball query / three_nn / knn is rounded ---------------------------------
@@ -630,6 +630,22 @@ int g4d_knn_f32(int b, int p1, int p2, int k, const float *queries, const float 
  * "inf -> 0" fix-ups.  W (F,V,J); idx / dists (F/frames_per_clip, Vg, K) from g4d_knn_f32.  K <= 256, J <= 64. */
 int g4d_knn_blend_weights_f32(int frames, int frames_per_clip, int vg, int v, int k, int j, const float *W, const int *idx,
                               const float *dists, float *out, g4d_stream_t stream);
+
+/* Nearest-vertex two-stage garment skinning of the MGN model variant (modules/mesh_encoder.py:529-585, csrc/mgn_skin.hip), one launch.
+ * F = clips * frames_per_clip frames, clip c = f / frames_per_clip.  Per (frame f, garment vertex g):
+ *   q  = garment[f,g] + root[c]                                  (one fp32 add)
+ *   nn = the nearest of tpose[c, 0..V-1] to q: index and squared distance equal g4d_knn_f32(K = 1) on the same q bit for bit, in
+ *        every distance-contraction mode (same rounding, same (distance, index) order: ties go to the lowest index)
+ *   s  = M_inv[:3,:3] q + M_inv[:3,3],  M_inv = sum_j W[f,nn,j] inv_A[f,j]      (stage 1: the un-posed garment)
+ *   p  = M[:3,:3] s + M[:3,3],          M     = sum_j W[f,nn,j] A[f,j]          (posed)
+ * Summation order: every entry of M_inv / M is acc = fma(W[f,nn,j], T_j[r][k], acc) for j = 0, 1, ..., J-1 from acc = 0; the row
+ * products are fma(M[r][2], z, fma(M[r][1], y, fma(M[r][0], x, M[r][3]))).  Only the nearest vertex's row of W is read.
+ * garment (F,Vg,3); root (clips,3); tpose (clips,V,3); W (F,V,J); inv_A, A (F,J,4,4), 16-byte aligned.
+ * Outputs: nn_idx (F,Vg) int32, nn_dist (F,Vg), stage1 (F,Vg,3), posed (F,Vg,3).  Any V >= 1 (the T-pose streams through LDS in
+ * tiles), 1 <= J <= 64, any Vg and frames_per_clip; nothing is launched when clips, frames_per_clip or Vg is 0. */
+int g4d_mgn_skin_f32(int clips, int frames_per_clip, int vg, int v, int j, const float *garment, const float *root, const float *tpose,
+                     const float *W, const float *inv_A, const float *A, int *nn_idx, float *nn_dist, float *stage1, float *posed,
+                     g4d_stream_t stream);
 
 /* One Jacobi smoothing step of the blended weights over the garment mesh (modules/mesh_encoder.py:385-390):
  * out (F,Vg,C) = S + coeff * (adj (CSR) . S).  out must not alias S (ping-pong two buffers for the 100 steps). */
