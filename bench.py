@@ -4,6 +4,8 @@
   python bench.py --gpus N --steps K --warmup W          (N>1: one rank per GPU under torch.distributed.run -- started by the
                                                           driver, or by bench.py itself when it finds no WORLD_SIZE in its environment)
   python bench.py ... --dump-outputs DIR                 (also writes the last timed step's outputs as DIR/<name>.npy)
+  python bench.py ... --full                             (also the secondary measurements: latency, drop-in route, per-launch
+                                                          table and rooflines, CPU baseline, per-rank rates)
 
 A "step" is one pass of the hot path over one batch of synthetic input: BASELINE config 2 -- B=8 clouds of
 N=8192 points through the Pointnet2MSGSEG-spec encoder (3x SA-MSG: FPS + ball query + grouped shared MLP + max
@@ -26,10 +28,13 @@ The pool, the pose parameters and the weights are seeded: the same arguments giv
 --dump-outputs DIR: after the timed region, the outputs of the last timed step (what StepFuture.result() hands its caller:
 sem_logits (8, N, classes) and, with lbs(), verts (8, 6890, 3) and joints (8, J, 3)) are written as DIR/<name>.npy in float32.
 
-Output: ONE JSON line (rank 0) with the contract fields + `roofline` (dominant kernel by GPU time = FPS level 1, a LATENCY-
-bound kernel, measured with HIP events in an instrumented eager pass inside this script) + `roofline_mfma` (heaviest MFMA
-launch) + `whole_path` (the SURVEY 8(d) fractions of the step as a whole) + `latency_ms_single_stream` + `cpu_baseline`
-(the CPU oracle timed on this box per BASELINE.md section 3: 1 thread and all cores, warm-up, medians, CPU model).
+Output: ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps, dumps (if asked) and prints the contract
+fields + `config` + `whole_path` (the SURVEY 8(d) fractions of the step as a whole, from `value`); nothing else runs.
+--full adds the secondary measurements, each of which takes runs of its own after the timed region: `frames_per_s_by_rank`
+(N>1), `latency_ms_single_stream` / `latency_ms_one_call`, `dropin` (the reference's call forms through the same executor),
+`launches` + `roofline*` (an instrumented eager pass with HIP events around every C-ABI call; also fills
+`whole_path.mfma_frac_executed`) and `cpu_baseline` (the CPU oracle timed on this box per BASELINE.md section 3: 1 thread and
+all cores, warm-up, medians, CPU model).  --no-dropin and --no-cpu-baseline leave out those legs of a --full run.
 """
 import argparse
 import json
@@ -60,12 +65,14 @@ def parse():
                                                               "reference's own fold of (8 clips, 30 frames) into one batch, modules/mesh_encoder.py:133")
     ap.add_argument("--streams", type=int, default=8, help="calls in flight per GPU, each a captured hipGraph on its own stream (profiles/r04_coalesce_by_streams.txt)")
     ap.add_argument("--no-graph", action="store_true", help="launch eagerly instead of replaying hipGraphs")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-frames", type=int, default=16, help="frames per sample the CPU oracle is timed on with all cores")
+    ap.add_argument("--full", action="store_true", help="also run the secondary measurements after the timed region (latency, drop-in route, "
+                                                         "per-launch table and rooflines, CPU baseline, per-rank rates); off: the headline line only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--cpu-frames", type=int, default=16, help="frames per sample the CPU oracle is timed on with all cores (--full)")
     ap.add_argument("--input-pool-mb", type=float, default=320.0, help="distinct input clouds rotated through, in MB (0 = replay the "
                                                                        "same resident batches: MALL-warm inputs)")
     ap.add_argument("--no-lbs", action="store_true")
-    ap.add_argument("--no-dropin", action="store_true", help="skip the `dropin` leg (the reference's operator-API call forms through the same executor)")
+    ap.add_argument("--no-dropin", action="store_true", help="with --full: skip the `dropin` leg (the reference's operator-API call forms through the same executor)")
     ap.add_argument("--precision", default="fp32", choices=["fp32", "bf16", "bf16x3"],
                     help="bf16 = BASELINE config 3: shared-MLP operands in bf16 (fp32 accumulate); default fp32 = config 2")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N>1 (nccl = RCCL; gloo only for "
@@ -625,9 +632,10 @@ def main():
         dt, last = timed_block()
         if args.dump_outputs and rank == 0:
             dump_outputs(args.dump_outputs, last)        # now: the slot's output buffers are reused by the calls that follow
+        # Everything from here to the result line is --full only: secondary measurements, each a run of its own after the timed region.
         # per-rank rate of the same K steps once more (rank 0 prints the spread: a straggling GPU shows here first)
         my_dt = None
-        if dist is not None:
+        if dist is not None and args.full:
             barrier()
             t0 = time.perf_counter()
             run_steps(first, args.steps)
@@ -644,7 +652,7 @@ def main():
         # single-batch latency: ONE B = 8 step alone on an otherwise idle chip (what a caller that cannot batch sees) -- a captured graph of
         # the path on 8 clouds, not the coalesced call
         lat = lat_call = None
-        if rank == 0:
+        if rank == 0 and args.full:
             one = StepPipeline(model, smpl, clouds_per_step=B_CLOUDS, n_points=N_POINTS, coalesce=1, streams=1, precision=args.precision,
                                device=dev, use_graph=not args.no_graph)
 
@@ -673,7 +681,7 @@ def main():
         #   (b) the reference's own loop over SA_modules / FP_modules / FC_layer (pointnet2encoder.py:127-141), every module dispatching on its
         #       own (no cross-level launch sharing), twins carrying the point-major layout between modules.
         dropin = None
-        if rank == 0 and world == 1 and not args.no_dropin:
+        if rank == 0 and world == 1 and args.full and not args.no_dropin:
             from garment4d_amd import tuning as _tuning
 
             def dropin_rate(tun, seconds):
@@ -727,9 +735,9 @@ def main():
                       "modules_route": "the reference's loop SA_modules[i](xyz, features) / FP_modules[i](...) / FC_layer(...) over this package's modules "
                                        "(pointnet2encoder.py:127-141), each module dispatching to its fused kernels on its own, + lbs()",
                       "clouds_per_call": B_CLOUDS * kco, "calls_in_flight": ns}
-        table = roof = None
+        table, roof = [], {}
         call_us = None
-        if rank == 0:
+        if rank == 0 and args.full:
             try:
                 table, roof, call_us = launch_table(model, smpl, pose_pool, pool, kco, args.precision)
             except Exception as e:   # the instrumented pass must never cost the headline line: the line then says what failed
@@ -759,8 +767,8 @@ def main():
                        "inputs": (f"rotating pool of {npool} distinct batches = {npool * B_CLOUDS * N_POINTS * 12 / 1e6:.0f} MB"
                                   f"{' (> 256 MB MALL)' if npool * B_CLOUDS * N_POINTS * 12 > 256e6 else ''}, each step's batch (and its betas / pose) copied "
                                   "into the call's input buffers on the call's stream inside the timed region"),
-                       "note": f"a step lasts longer than ms_per_step: {ns} calls of {kco} steps overlap (one B=8 step alone: latency_ms_single_stream; "
-                               "one coalesced call alone: latency_ms_one_call)",
+                       "note": f"a step lasts longer than ms_per_step: {ns} calls of {kco} steps overlap (--full reports one B=8 step alone: "
+                               "latency_ms_single_stream; one coalesced call alone: latency_ms_one_call)",
                        "device": torch.cuda.get_device_name(dev),
                        "collective_backend": None if dist is None else f"{args.backend} world_size={dist.get_world_size()} (barrier + max-reduce of the time only)",
                        "launcher": "self (bench.py re-executed under torch.distributed.run)" if os.environ.get("G4D_BENCH_SELF_LAUNCHED") else
@@ -785,7 +793,11 @@ def main():
                            "hbm_frac_of_fused_lower_bound": per_gpu * 8.0e6 / (HBM_PEAK_GBS * 1e9),
                            "per_frame": "2.22 GFLOP, 42.5 MB op-by-op traffic, ~8 MB fused lower bound (BASELINE.md section 2)"},
         }
-        if not args.no_cpu_baseline and world == 1:  # reported at N=1 only (same host cores at every N)
+        if not args.full:   # a plain run measured none of these (and leaves whole_path's executed-flop fields None: they come from the launch table)
+            for k in ("latency_ms_single_stream", "latency_frames_per_s", "latency_ms_one_call", "frames_per_s_by_rank", "dropin",
+                      "roofline", "roofline_mfma_all", "roofline_fps", "roofline_hbm", "launches"):
+                del line[k]
+        if args.full and not args.no_cpu_baseline and world == 1:  # reported at N=1 only (same host cores at every N)
             try:
                 line["cpu_baseline"] = cpu_baseline(args.cpu_frames, with_lbs)
             except Exception as e:

@@ -8,14 +8,14 @@ ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$ROOT/gpurun_out/profiles
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-B="python $ROOT/bench.py --no-cpu-baseline"
+B="python $ROOT/bench.py --full --no-cpu-baseline"
 STEP="python $ROOT/scripts/prof_step.py"
 # 0. the bench lines themselves (fp32 = BASELINE config 2, bf16 = config 3), builder-run; the driver's 20-step form; the B = 8 regime of round 3
-python $ROOT/bench.py --steps 160 > $OUT/${R}_bench_fp32.json 2> $OUT/bench_fp32.err
+python $ROOT/bench.py --full --steps 160 > $OUT/${R}_bench_fp32.json 2> $OUT/bench_fp32.err
 $B --steps 160 --precision bf16 > $OUT/${R}_bench_bf16.json 2> $OUT/bench_bf16.err
-python $ROOT/bench.py --steps 20 --warmup 4 > $OUT/${R}_bench_driver_style.json 2> $OUT/bench_driver.err
+python $ROOT/bench.py --full --steps 20 --warmup 4 > $OUT/${R}_bench_driver_style.json 2> $OUT/bench_driver.err
 $B --steps 160 --coalesce 1 --streams 20 > $OUT/${R}_bench_fp32_uncoalesced_20streams.json 2> /dev/null
-# 1. the default bench command under the kernel trace (the profiler serialises the streams)
+# 1. the --full bench command under the kernel trace (the profiler serialises the streams)
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench -o b -- $B --steps 60 > $OUT/bench.log 2>&1
 cp $OUT/bench/b_kernel_stats.csv $OUT/${R}_kernel_stats_bench_default.csv
 # 2. one call at a time, eager launches: per-kernel durations at 240 clouds per call (the executor's call) and at 8 (a caller that cannot batch)
@@ -57,10 +57,10 @@ python $ROOT/scripts/time_lbs.py 1 8 16 30 240 2>&1 | grep "lbs()" > $OUT/${R}_l
 # 7. frames/s over (steps coalesced per call) x (calls in flight)
 cd $ROOT
 {
-  echo "# bench.py --no-cpu-baseline --steps 12000 --coalesce k --streams ns: frames/s (us per B=8 step) | one call alone, ms"
+  echo "# bench.py --full --no-cpu-baseline --steps 12000 --coalesce k --streams ns: frames/s (us per B=8 step) | one call alone, ms"
   for cfg in "1 1" "1 8" "1 16" "1 20" "2 12" "4 8" "8 4" "8 6" "15 2" "15 4" "30 1" "30 2" "30 3" "30 4" "60 2"; do
     set -- $cfg
-    python bench.py --no-cpu-baseline --steps 12000 --coalesce $1 --streams $2 2>/dev/null | python -c "
+    python bench.py --full --no-cpu-baseline --steps 12000 --coalesce $1 --streams $2 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('k=%3d clouds/call=%4d calls in flight=%2d clouds in flight=%4d : %7.0f frames/s (%6.1f us/step) | %7.3f ms' % ($1, 8*$1, $2, 8*$1*$2, d['value'], d['ms_per_step']*1e3, d['latency_ms_one_call']))"

@@ -8,6 +8,8 @@ for key in ("roofline", "roofline_mfma_all", "roofline_fps"):
     print(key, {k: (round(v, 3) if isinstance(v, float) else v) for k, v in r.items() if k in ("kernel", "us", "avg_launch_us", "achieved", "frac", "mfma_busy", "traffic", "us_per_round", "share_of_call", "launches")})
 for r in d.get("roofline_hbm") or []:
     print("hbm/valu", r["entry"], round(r["us"], 1), "us frac", round(r.get("frac", 0), 3), r.get("mfma_frac"))
+if "launches" not in d:
+    sys.exit("no per-launch table: the line is from a plain run (bench.py --full adds it)")
 print("eager one stream us:", round(d["launches"]["eager_one_stream_us"], 1))
 for r in d["launches"]["table"]:
     print(f"{r['entry'][:36]:36s} {r['us']:8.1f} {str(r.get('bound')):8s} {str(r.get('frac')):6s} | {r['what'][:100]}")

@@ -40,3 +40,12 @@ def test_main_self_launches_only_without_a_launcher(monkeypatch):
     with pytest.raises(AssertionError, match="WORLD_SIZE=1"):
         bench.main()
     assert len(calls) == 1
+
+
+def test_full_is_off_by_default(monkeypatch):
+    """A plain run measures the headline only; the secondary measurements run under --full."""
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert bench.parse().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--full"])
+    assert bench.parse().full is True

@@ -3,6 +3,7 @@ import json
 import os
 import subprocess
 import sys
+import time
 
 import numpy as np
 import pytest
@@ -12,7 +13,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_prints_one_json_line_with_the_contract_keys():
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "8", "--warmup", "1", "--cpu-frames", "2"],
+    """--full: the headline line plus every secondary measurement (latency, drop-in route, launch table, rooflines, CPU baseline)."""
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "8", "--warmup", "1", "--cpu-frames", "2", "--full"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.strip()]
@@ -45,6 +47,33 @@ def test_bench_prints_one_json_line_with_the_contract_keys():
     for k in ("value", "unit", "cores", "kind", "sample"):
         assert k in c, k
     assert c["kind"] == "port" and c["value"] > 0 and d["value"] > 10 * c["value"]
+
+
+FULL_ONLY = ("latency_ms_single_stream", "latency_frames_per_s", "latency_ms_one_call", "frames_per_s_by_rank", "dropin", "roofline",
+             "roofline_mfma_all", "roofline_fps", "roofline_hbm", "launches", "cpu_baseline")
+
+
+def test_plain_bench_measures_the_headline_only():
+    """Without --full the run sets up, warms up, times --steps steps and prints the line: the contract fields and none of the
+    secondary measurements, with at most 30 s of the whole run spent outside the warm-up and timed steps."""
+    steps, warmup = 8, 1
+    t0 = time.perf_counter()
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", str(warmup)],
+                       capture_output=True, text=True, timeout=600, cwd=ROOT)
+    wall = time.perf_counter() - t0
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [l for l in p.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data",
+              "config", "whole_path"):
+        assert k in d, k
+    assert d["n_gpus"] == 1 and d["steps"] == steps and d["warmup"] == warmup and d["higher_is_better"] is True
+    assert d["unit"] == "frames/s" and d["value"] > 1000 and d["dtype"] == "f32" and d["data"] == "synthetic"
+    assert d["config"]["timed_steps"] == steps and abs(d["ms_per_step"] - d["config"]["timed_seconds"] * 1e3 / steps) < 1e-9
+    assert not set(FULL_ONLY) & set(d), set(FULL_ONLY) & set(d)
+    assert d["whole_path"]["mfma_frac"] > 0 and d["whole_path"]["mfma_frac_executed"] is None
+    assert wall - (steps + warmup) * d["ms_per_step"] * 1e-3 < 30.0, wall
 
 
 def _one_json_line(p):
