@@ -63,7 +63,8 @@ class Pointnet2MSGSEG(nn.Module):
         stacks = [m for sa in self.SA_modules for m in sa.mlps] + [fp.mlp for fp in self.FP_modules] + [self.FC_layer]
         if self.global_feat:
             stacks += list(self.Middle_modules.mlps)
-        if _T().dropin_whole_model and fused_route(self, stacks, pointcloud) and all(sa.pool_method in ("max_pool", "avg_pool") for sa in self.SA_modules):
+        sas = list(self.SA_modules) + ([self.Middle_modules] if self.global_feat else [])
+        if _T().dropin_whole_model and fused_route(self, stacks, pointcloud) and all(sa.pool_method in ("max_pool", "avg_pool") for sa in sas):
             # the drop-in route of north_star: same kernels and launches as forward_fused(); precision = the fused.precision() in force (fp32)
             return self._forward_fused(pointcloud.contiguous(), channel_major=True)
         xyz, features = self._break_up_pc(pointcloud)
@@ -83,7 +84,7 @@ class Pointnet2MSGSEG(nn.Module):
         `channel_major` (then converted to the reference's (B, C_l, N_l) at the boundary).
         precision="bf16" (BASELINE config 3) runs the shared MLPs with bf16 operands / fp32 accumulation; sampling,
         grouping, interpolation weights and all tensors crossing the API stay fp32."""
-        assert not self.training and precision in fused.PRECISIONS
+        assert not any(m.training for m in self.modules()) and precision in fused.PRECISIONS
         with fused.precision(precision):   # per-thread context, not a process global
             return self._forward_fused(pointcloud, channel_major)
 

@@ -762,12 +762,18 @@ def sa_forward(sa, xyz, feats_pm=None, new_xyz=None, grid=None, idxs=None):
     """Fused PointnetSAModule(MSG).forward (pointnet2_modules.py:19-55), eval mode.
     xyz (B,N,3); feats_pm (B,N,C) POINT-major or None  ->  (new_xyz (B,P,3)|None, feats (B,P,sum Cout) point-major).
     grid: passed to ball_query_msg (None = automatic, or a pre-built (workspace, rmax) pair)."""
-    assert not sa.training, "fused path is eval-mode only (train-mode BN needs batch statistics)"
+    assert not any(m.training for m in sa.modules()), "fused path is eval-mode only (train-mode BN needs batch statistics)"
     _chk(xyz)
     B, N, _ = xyz.shape
     C = 0 if feats_pm is None else _chk(feats_pm).shape[2]
     pool = {"max_pool": 1, "avg_pool": 2}[sa.pool_method]
     packed = [pack_conv_stack(m) for m in sa.mlps]
+    if feats_pm is not None and tuple(feats_pm.shape[:2]) != (B, N):
+        raise RuntimeError(f"set abstraction: features of {tuple(feats_pm.shape[:2])} (batch, points) for xyz of ({B}, {N})")
+    for g, layers in zip(sa.groupers, packed):
+        cin = (3 if (g.use_xyz or feats_pm is None) else 0) + C
+        if layers[0].K != cin:   # the op-by-op route's first convolution raises on this; the kernels would read part of W
+            raise RuntimeError(f"set abstraction: {cin} input channels, but the first layer expects {layers[0].K}")
     ctot = sum(p[-1].Cout for p in packed)
     stream = _lib.stream_ptr()
     if sa.npoint is not None:
@@ -930,13 +936,20 @@ def fp_forward(fp, unknown, known, unknow_feats_pm, known_feats_pm, head=None, u
     unknown (B,n,3), known (B,m,3)|None, unknow_feats_pm (B,n,C1)|None, known_feats_pm (B,m,C2) -> (B,n,Cout).
     With `head` (an FC stack of Conv1d blocks) returns (features, head(features)), fused into the same launch when
     the widths allow."""
-    assert not fp.training, "fused path is eval-mode only"
+    assert not any(m.training for m in fp.modules()), "fused path is eval-mode only"
     _chk(unknown)
     _chk(known_feats_pm)
     B, n, _ = unknown.shape
     layers = pack_conv_stack(fp.mlp)
     stream = _lib.stream_ptr()
     C1 = 0 if unknow_feats_pm is None else _chk(unknow_feats_pm).shape[2]
+    m_want = 1 if known is None else known.shape[1]
+    if tuple(known_feats_pm.shape[:2]) != (B, m_want) or (known is not None and known.shape[0] != B):
+        raise RuntimeError(f"feature propagation: known features of {tuple(known_feats_pm.shape[:2])} (batch, points) for {m_want} known points")
+    if unknow_feats_pm is not None and tuple(unknow_feats_pm.shape[:2]) != (B, n):
+        raise RuntimeError(f"feature propagation: skip features of {tuple(unknow_feats_pm.shape[:2])} (batch, points) for ({B}, {n})")
+    if C1 + known_feats_pm.shape[2] != layers[0].K:   # the op-by-op route's first convolution raises on this
+        raise RuntimeError(f"feature propagation: {C1} + {known_feats_pm.shape[2]} input channels, but the first layer expects {layers[0].K}")
     out = torch.empty((B, n, layers[-1].Cout), dtype=torch.float32, device=unknown.device)
     if known is None:
         # broadcast of a single known feature over n points (pointnet2_modules.py:146)

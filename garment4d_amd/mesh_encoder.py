@@ -13,8 +13,8 @@ Inference only.  What the constructor needs fro
 and the garment template OBJ, both part of the CLOTH3D-derived data set that is not available here) can be given either
 through the reference's cfg (`cfg.GARMENT.PCACOMPONENTSFILE`, `cfg.GARMENT.TEMPLATE`) or as arrays.  Frames may be
 sharded over ranks: pass `group` / `frame_ids`; the exchanges are the clip max of the garment summary (all-reduce MAX of
-(clips, 512)) and the all-gather inside the temporal attention (garment4d_amd/dist.py).  PARITY UNPINNED as a whole:
-mesh_encoder.py cannot be imported here (chamferdist, openmesh, torch_scatter are absent); its pieces are pinned."""
+(clips, 512)) and the all-gather inside the temporal attention (garment4d_amd/dist.py).  PCAGarmentEncoderSeg is pinned as a whole
+against the reference's own class (tests/golden/encoder.npz); the rest of the model through its pieces (refine.npz, mgn.npz)."""
 import pickle
 
 import numpy as np
@@ -33,6 +33,12 @@ from .refine import GarmentRefinementHead
 
 label_dict = {"Body": 1, "Skirt": 2, "Dress": 3, "Jumpsuit": 4, "Top": 5, "Trousers": 6, "Tshirt": 7}  # utils/dataloader.py:15-23
 class_num = 7
+
+
+def _any_training(module):
+    """True if the module or any submodule is in train mode (e.g. a BatchNorm switched back to train() for recalibration): the fused
+    kernels fold BatchNorm from the running statistics, so such a model must not run here."""
+    return any(m.training for m in module.modules())
 
 
 def _pack_plain_stack(seq):
@@ -116,7 +122,7 @@ class PCAGarmentEncoderSeg(nn.Module):
     def forward(self, x, body_model=None, batch=None, *, nbatch=None, T=None, frame_ids=None, group=None):
         """x (nbatch, T, N, >=3) -- or, frame-sharded, the local frames (F_local, N, >=3) with nbatch, T and the global ids
         of the local frames.  Same output keys as the reference."""
-        assert not torch.is_grad_enabled() and not self.training, "inference only: model.eval() under torch.no_grad()"
+        assert not torch.is_grad_enabled() and not _any_training(self), "inference only: model.eval() (every submodule) under torch.no_grad()"
         assert x.size(-1) >= 3
         if x.dim() == 4:
             nbatch, T = x.shape[0], x.shape[1]
@@ -193,7 +199,7 @@ class PCALBSGarmentUseSegEncoderSeg(GarmentRefinementHead):
             return self._forward(x, body_model, batch)
 
     def _forward(self, x, body_model, batch):
-        assert not torch.is_grad_enabled() and not self.training, "inference only: model.eval() under torch.no_grad()"
+        assert not torch.is_grad_enabled() and not _any_training(self), "inference only: model.eval() (every submodule) under torch.no_grad()"
         import scipy.sparse as sp
         nbatch, T = x.size(0), x.size(1)
         dev = x.device
@@ -226,7 +232,7 @@ class PCALBSGarmentUseSegEncoderSeg(GarmentRefinementHead):
         (nbatch,V,3), `Tpose_smpl_root_joints_torch` (nbatch,3), `clip_J_regressor` (nbatch,J,V), `clip_lbs_weights`
         (nbatch,V,J) = the first frame's tables of each clip).  Exchanges: all-reduce MAX of the (nbatch, 512) garment summary;
         one all-gather of (frames, Vg, 128) per attention round.  Same output keys as `forward`, for the local frames."""
-        assert not torch.is_grad_enabled() and not self.training, "inference only: model.eval() under torch.no_grad()"
+        assert not torch.is_grad_enabled() and not _any_training(self), "inference only: model.eval() (every submodule) under torch.no_grad()"
         dev = x.device
         ids = [int(i) for i in frame_ids]
         assert ids == sorted(ids) and len(ids) == x.shape[0]
@@ -319,7 +325,7 @@ class PCALBSGarmentUseSegEncoderSegMGN(nn.Module):
         """x (nbatch, T, N, 3); body_model needs `.parents`; batch holds the reference's keys (`Tpose_smpl_vertices_torch`,
         `Tpose_smpl_root_joints_torch`, `zeropose_smpl_vertices_torch`, `pose_torch`, `T_J_regressor`, `T_lbs_weights`) with the same
         leading (nbatch, T) as x.  precision as in PCALBSGarmentUseSegEncoderSeg.forward (the encoder's MLP operands only)."""
-        assert not torch.is_grad_enabled() and not self.training, "inference only: model.eval() under torch.no_grad()"
+        assert not torch.is_grad_enabled() and not _any_training(self), "inference only: model.eval() (every submodule) under torch.no_grad()"
         nbatch, T = x.size(0), x.size(1)
         dev = x.device
         with fused.precision(precision):
@@ -341,7 +347,7 @@ class PCALBSGarmentUseSegEncoderSegMGN(nn.Module):
         (`Tpose_smpl_vertices_torch` (nbatch,V,3), `Tpose_smpl_root_joints_torch` (nbatch,3)).  The one exchange is the encoder's
         all-reduce MAX of the (nbatch, 512) garment summary; everything after it is per frame.  Same output keys as `forward`, for the
         local frames (`lbs_pred_garment_v` / `lbs_stage1_pred_garment_v` (F_local,Vg,3), `lbs_nn` with (F_local,Vg,1))."""
-        assert not torch.is_grad_enabled() and not self.training, "inference only: model.eval() under torch.no_grad()"
+        assert not torch.is_grad_enabled() and not _any_training(self), "inference only: model.eval() (every submodule) under torch.no_grad()"
         dev = x.device
         ids = [int(i) for i in frame_ids]
         assert ids == sorted(ids) and len(ids) == x.shape[0]

@@ -71,7 +71,7 @@ class StepPipeline:
         J_regressor, parents, lbs_weights (HIP tensors) or None for the encoder alone.  tuning: the garment4d_amd.tuning.Tuning this
         executor runs under (default: the one in force where it is constructed) -- held for its lifetime, applied around every call it
         launches or captures; two executors in one process can carry different ones."""
-        assert coalesce >= 1 and streams >= 1 and not model.training
+        assert coalesce >= 1 and streams >= 1 and not any(m.training for m in model.modules())
         self.tuning = tuning if tuning is not None else _tuning.current()
         self.model, self.smpl, self.B, self.N, self.k = model, smpl, int(clouds_per_step), int(n_points), int(coalesce)
         self.precision, self.pose2rot, self.use_graph, self.encoder_call = precision, pose2rot, use_graph, encoder_call

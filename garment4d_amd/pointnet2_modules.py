@@ -32,8 +32,10 @@ def op_by_op():
 
 
 def fused_route(module, stacks, *tensors):
-    """Does this forward() call go to the fused kernels?  eval mode, autograd off, fp32 HIP tensors, every stack packable."""
-    if module.training or torch.is_grad_enabled() or not _T().dropin_fused:
+    """Does this forward() call go to the fused kernels?  eval mode -- of `module` and of EVERY submodule: a BatchNorm switched back to
+    train() inside an eval() model (BN recalibration) needs batch statistics and updates its running stats, which only the op-by-op
+    route does --, autograd off, fp32 HIP tensors, every stack packable."""
+    if any(m.training for m in module.modules()) or torch.is_grad_enabled() or not _T().dropin_fused:
         return False
     for t in tensors:
         if t is not None and not (t.is_cuda and t.dtype == torch.float32):

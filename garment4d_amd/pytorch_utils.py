@@ -72,7 +72,8 @@ class Conv1d(_ConvBase):
     def forward(self, x):
         """(B, Cin, N) -> (B, Cout, N).  eval() + no_grad on an fp32 HIP tensor: conv + BN + ReLU as ONE contraction launch
         (fused.linear) on the point-major twin of `x`; otherwise torch's layers, as the reference (trainable)."""
-        if (not self.training) and (not torch.is_grad_enabled()) and x.dim() == 3 and x.is_cuda and x.dtype == torch.float32:
+        # every submodule in eval(): a BatchNorm switched back to train() (recalibration) needs batch statistics -> torch's layers
+        if (not any(m.training for m in self.modules())) and (not torch.is_grad_enabled()) and x.dim() == 3 and x.is_cuda and x.dtype == torch.float32:
             from . import fused
             from .tuning import current as _T
             if _T().dropin_fused:

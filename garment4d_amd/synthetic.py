@@ -239,3 +239,66 @@ def mgn_golden_case(seed=90, nbatch=2, T=3):
     pred_template = (tpose_garment[:, None] + rng.standard_normal((nbatch, T, Vg, 3)) * 0.01).astype(F32)
     return dict(seed=seed, nbatch=nbatch, T=T, Vg=Vg, batch=batch, body=sc["body"], template_verts=gv, template_faces=gq,
                 tpose_garment=tpose_garment, garment_summary=garment_summary, pred_template=pred_template)
+
+
+def encoder_state_dict(shapes, seed=0):
+    """Seeded weights for a PointNet++ encoder / PCAGarmentEncoderSeg given its state-dict {key: shape} (keys drawn in sorted order, so
+    the reference's model and this package's give the same values).  Multi-dimensional weights: kaiming-normal over the fan-in.  Every
+    BatchNorm (a prefix with a `running_mean`): scale +-U[0.5,1.5] (random sign), shift N(0,0.1), running mean N(0,0.2), running
+    variance U[0.5,1.5] -- including the plain nn.BatchNorm1d layers of the PCA head, which encoder.seed_encoder leaves at N(0,0.1) and
+    so almost switches off.  Other vectors (conv biases): N(0,0.1).  numpy; num_batches_tracked = 0 (int64), everything else fp32."""
+    rng = np.random.default_rng(seed)
+    bn = {k[:-len("running_mean")] for k in shapes if k.endswith("running_mean")}
+    sd = {}
+    for k in sorted(shapes):
+        shape = tuple(int(s) for s in shapes[k])
+        prefix, leaf = k[:k.rfind(".") + 1], k[k.rfind(".") + 1:]
+        if leaf == "num_batches_tracked":
+            sd[k] = np.zeros(shape, np.int64)
+        elif prefix in bn:
+            if leaf == "weight":
+                v = (rng.random(shape) + 0.5) * np.where(rng.random(shape) < 0.5, -1.0, 1.0)
+            elif leaf == "running_var":
+                v = rng.random(shape) + 0.5
+            else:
+                v = rng.standard_normal(shape) * (0.2 if leaf == "running_mean" else 0.1)
+            sd[k] = v.astype(F32)
+        elif len(shape) > 1:
+            sd[k] = (rng.standard_normal(shape) * np.sqrt(2.0 / np.prod(shape[1:]))).astype(F32)
+        else:
+            sd[k] = (rng.standard_normal(shape) * 0.1).astype(F32)
+    return sd
+
+
+def state_dict_checksum(sd):
+    """Per-key float64 sums in sorted key order: detects drift of a seeded state dict between a generator and its tests."""
+    return np.array([float(np.asarray(sd[k], dtype=np.float64).sum()) for k in sorted(sd)])
+
+
+def encoder_golden_case(seed=120):
+    """The inputs of tests/golden/encoder.npz (written by tests/golden/make_golden_encoder.py, which runs the reference's own
+    PCAGarmentEncoderSeg and Pointnet2MSGSEG on them).
+    E1: two clips of two N = 6890 frames whose geometries give the garment class very different logit ranges under the seeded weights:
+    frame 0 = 70 % points on a line interleaved with 30 % isolated far points, frame 1 = the unit cube, frame 2 = a 0.01-wide cube,
+    frame 3 = a 0.3-wide cube; the PCA basis (72 random components, a non-zero mean, a per-coordinate scale) and a 16 x 16 quad
+    cylinder template.  E2/E3: a (2, 2048, 6) cloud (xyz in the unit cube + three N(0,1) feature channels)."""
+    rng = np.random.default_rng(seed)
+    N = 6890
+    line = unit_cloud(1, N, seed=seed + 1)[0] * np.array([3, 0, 0], F32)
+    far = unit_cloud(1, N, seed=seed + 2)[0] * F32(20) + F32(100)
+    f0 = np.where((rng.random(N) < 0.7)[:, None], line, far)
+    frames = [f0, unit_cloud(1, N, seed=seed + 3)[0], unit_cloud(1, N, seed=seed + 4)[0] * F32(0.01),
+              unit_cloud(1, N, seed=seed + 5)[0] * F32(0.3)]
+    x = np.stack(frames).astype(F32).reshape(2, 2, N, 3)
+    gv, gq = quad_cylinder(16, 16)
+    gv = (gv * np.array([1.0, 0.45, 0.7], dtype=F32) + np.array([0, -0.2, 0], dtype=F32)).astype(F32)
+    pca = dict(components=(rng.standard_normal((72, gv.size)) * 0.01).astype(F32),
+               mean=(gv.reshape(-1) + rng.standard_normal(gv.size) * 0.01).astype(F32),
+               explained=rng.random(72), ss_scale=(0.5 + rng.random(gv.size)).astype(np.float64))
+    pc = np.concatenate([unit_cloud(2, 2048, seed=seed + 6), rng.standard_normal((2, 2048, 3)).astype(F32)], -1).astype(F32)
+    return dict(seed=seed, nbatch=2, T=2, N=N, x=x, pca=pca, template=(gv, gq), pc=pc)
+
+
+def encoder_golden_checksum(case):
+    items = [case["x"], case["pc"], case["template"][0], case["template"][1]] + [case["pca"][k] for k in sorted(case["pca"])]
+    return np.array([float(np.asarray(a, dtype=np.float64).sum()) for a in items])

@@ -3,8 +3,8 @@
 `PCALBSGarmentUseSegEncoderSeg.forward` (:412-487) -- composed from the pinned pointnet2 / lbs / gcn oracles.
 Pinned in parts: compute_vnorms and the refinement loop + garment skinning (through refine_oracle) against the reference's own
 utils/mesh_utils.py and modules/mesh_encoder.py (tests/golden/refine.npz, make_golden_refine.py); the SA / FP / head stack against
-modules.npz.  NOT reference-run: PCAGarmentEncoderSeg.forward's wiring as a whole (its constructor needs the PCA pickle and the template
-OBJ, mesh_encoder.py:89-99) and calc_segmentation_results -- those follow the source text (:109-169)."""
+modules.npz; garment_encoder_forward (PCAGarmentEncoderSeg.forward's wiring as a whole, incl. calc_segmentation_results) against the
+reference's own class run on a PCA pickle and template OBJ written to a temporary directory (tests/golden/encoder.npz)."""
 import numpy as np
 
 from . import modules_oracle as MO

@@ -14,6 +14,7 @@ import pytest
 import torch
 
 from conftest import sub_state_dict
+from encoder_golden import reference_encoder_loop
 from garment4d_amd import fused, pointnet2_modules as PM, pytorch_utils as pt, synthetic as syn
 from garment4d_amd.encoder import Pointnet2MSGSEG, seed_encoder
 from oracle import modules_oracle as MO
@@ -93,23 +94,6 @@ def test_module_forwards_dispatch_to_fused_kernels_and_match_reference_goldens(g
         ft = copy.deepcopy(sa).train()(xyz, feats)[1]
     assert not took_fused(ft)
     close(ft, g["samsg_train"], tol=1e-4)
-
-
-def reference_encoder_loop(model, pc):
-    """The forward of modules/pointnet2encoder.py:112-145, statement for statement, over whatever modules `model` holds -- this is what
-    the reference's file runs when it imports this package's pointnet2_modules / pytorch_utils in place of its own."""
-    xyz = pc[..., 0:3].contiguous()
-    features = pc[..., 3:].transpose(1, 2).contiguous() if pc.size(-1) > 3 else None
-    l_xyz, l_features = [xyz], [features]
-    for i in range(len(model.SA_modules)):
-        li_xyz, li_features = model.SA_modules[i](l_xyz[i], l_features[i])
-        l_xyz.append(li_xyz)
-        l_features.append(li_features)
-    middle = model.Middle_modules(l_xyz[-1], l_features[-1])[1] if model.global_feat else None
-    for i in range(-1, -(len(model.FP_modules) + 1), -1):
-        l_features[i - 1] = model.FP_modules[i](l_xyz[i - 1], l_xyz[i], l_features[i - 1], l_features[i])
-    sem_logits = model.FC_layer(l_features[0]).transpose(1, 2).contiguous()
-    return middle, sem_logits, l_features, l_xyz
 
 
 @pytest.mark.parametrize("global_feat,cin", [(False, 0), (True, 0), (True, 3)])
