@@ -54,6 +54,12 @@ SIGNATURES = {
     "g4d_tuning_set_thread": [ctypes.c_char_p, ctypes.c_longlong, _I],
     "g4d_interp_concat_f32": [_I, _I, _I, _I, _I, _vp, _vp, _vp, _vp, _vp, _vp],
     "g4d_spmm_rows_f32": [_I, _I, _I, _vp, _vp, _vp, _vp, _vp, _I, _vp, _vp],
+    "g4d_spmm_rows_grad_f32": [_I, _I, _I, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "g4d_col_sum_rows_ws_bytes": [_LL, _I],
+    "g4d_col_sum_rows_f32": [_LL, _I, _vp, _vp, _vp, _vp, _vp],
+    "g4d_gemm_tn_slice_rows": [_LL, _I, _I],
+    "g4d_gemm_tn_ws_bytes": [_LL, _I, _I],
+    "g4d_gemm_tn_f32": [_LL, _I, _I, _I, _vp, _vp, _vp, _vp, _vp],
     "g4d_gcn_agg_linear_f32": [_I, _I, _I, _vp, _vp, _vp, _vp, _vp, _I, _vp, _vp, _I, _vp, _vp],
     "g4d_gcn_agg_linear_meta_f32": [_I, _I, _I, _vp, _vp, _vp, _vp, _vp, _I, _vp, _vp, _I, _vp, _vp, _vp],
     "g4d_gcn_tile_meta_bytes": [_I],
@@ -126,7 +132,7 @@ SIGNATURES = {
 _lib = None
 
 
-RESTYPES = {"g4d_mlp_args_size": ctypes.c_uint, "g4d_sa_table_ws_bytes": ctypes.c_longlong, "g4d_gcn_tile_meta_bytes": ctypes.c_longlong, "g4d_frag_bf16_elems": ctypes.c_longlong, "g4d_lbs_mfma_ws_bytes": ctypes.c_longlong, "g4d_three_nn_pruned_ws_bytes": ctypes.c_longlong, "g4d_temporal_attention_scratch_floats": ctypes.c_size_t, "g4d_ball_grid_bytes": ctypes.c_size_t, "g4d_ball_query_lanes_qsort_bytes": ctypes.c_size_t}   # everything else returns an int status
+RESTYPES = {"g4d_mlp_args_size": ctypes.c_uint, "g4d_col_sum_rows_ws_bytes": ctypes.c_longlong, "g4d_gemm_tn_slice_rows": ctypes.c_longlong, "g4d_gemm_tn_ws_bytes": ctypes.c_longlong, "g4d_sa_table_ws_bytes": ctypes.c_longlong, "g4d_gcn_tile_meta_bytes": ctypes.c_longlong, "g4d_frag_bf16_elems": ctypes.c_longlong, "g4d_lbs_mfma_ws_bytes": ctypes.c_longlong, "g4d_three_nn_pruned_ws_bytes": ctypes.c_longlong, "g4d_temporal_attention_scratch_floats": ctypes.c_size_t, "g4d_ball_grid_bytes": ctypes.c_size_t, "g4d_ball_query_lanes_qsort_bytes": ctypes.c_size_t}   # everything else returns an int status
 
 
 class G4DError(RuntimeError):

@@ -14,7 +14,15 @@ csrc/gcn_fused.hip): the activation between two layers stays in LDS (window of n
 tile instead of one L2 read per neighbour).  240 x 4096 rows, 128 -> 128: ~470 us against 344 (SpMM) + 404 (contraction); the
 323 -> 128 -> 128 -> 128 -> 3 stack 3.3 -> 2.12 ms (scripts/time_gcn_stack.py).  (An earlier fused kernel aggregating in the
 LOADER of the contraction, g4d_gcn_linear_f32, redoes the aggregation per 64-channel tile and was slower than two launches.)
-Inference only: no autograd graph is built.
+
+Gradients (opt-in: tuning.Tuning.gcn_autograd, environment G4D_GCN_AUTOGRAD; off by default, and then a grad-requiring call raises
+NotImplementedError as it always did).  With the switch on, a call that needs gradients runs the layer as a torch.autograd.Function whose
+forward is the two launches above (the same bits as under no_grad) and whose backward runs csrc/gcn_grad.hip: with G = dY masked by the
+fused ReLU (Y > 0),  dS = Ahat^T G (g4d_spmm_rows_grad_f32 over the CSR of Ahat^T, built once per adjacency),  db = column sums of G
+(g4d_col_sum_rows_f32),  dW = X^T dS (g4d_gemm_tn_f32: MFMA contraction along the rows, slice partials added in a fixed order) and
+dX = dS W^T (g4d_linear_f32 with W packed as the transposed weight).  Every one of them is deterministic; a gradient nobody needs is not
+launched.  gcn_stack_forward chains these per-layer functions under grad (the fused aggregate+contract launches keep the activation in LDS
+and remain the inference route).  The adjacency is a constant and gets no gradient.
 """
 import math
 import os
@@ -73,12 +81,8 @@ def adjacency_from_faces(faces, num_verts):
     return normalize(adjacency_old_from_faces(faces, num_verts) + sp.eye(num_verts))
 
 
-def _to_csr(adj, device):
-    """torch sparse (COO/CSR) or scipy sparse -> (rowptr, colidx, vals) int32/float32 on `device`, cached per object."""
-    key = (id(adj), str(device))
-    hit = _csr_cache.get(key)
-    if hit is not None and hit[0] is adj:
-        return hit[1]
+def _scipy_csr(adj):
+    """torch sparse (COO/CSR) or scipy sparse -> scipy CSR with sorted column indices."""
     if isinstance(adj, torch.Tensor):
         a = adj.detach().cpu()
         a = a.coalesce() if a.layout == torch.sparse_coo else a.to_sparse_coo().coalesce()
@@ -87,11 +91,45 @@ def _to_csr(adj, device):
     else:
         m = adj.tocsr()
     m.sort_indices()
+    return m
+
+
+def _csr_tensors(m, device):
+    return (torch.from_numpy(m.indptr.astype(np.int32)).to(device), torch.from_numpy(m.indices.astype(np.int32)).to(device),
+            torch.from_numpy(m.data.astype(np.float32)).to(device), m.shape[0])
+
+
+def _to_csr(adj, device):
+    """torch sparse (COO/CSR) or scipy sparse -> (rowptr, colidx, vals) int32/float32 on `device`, cached per object."""
+    key = (id(adj), str(device))
+    hit = _csr_cache.get(key)
+    if hit is not None and hit[0] is adj:
+        return hit[1]
+    m = _scipy_csr(adj)
     if len(_csr_cache) > 32:
         _csr_cache.clear()
-    csr = (torch.from_numpy(m.indptr.astype(np.int32)).to(device), torch.from_numpy(m.indices.astype(np.int32)).to(device),
-           torch.from_numpy(m.data.astype(np.float32)).to(device), m.shape[0])
+    csr = _csr_tensors(m, device)
     _csr_cache[key] = (adj, csr)
+    return csr
+
+
+_csr_t_cache = {}
+
+
+def _to_csr_t(adj, device):
+    """The CSR of adj^T -- (rowptr, colidx, vals, n) like _to_csr, cached per adjacency object: row u lists the v with adj[v, u] != 0 in
+    ASCENDING v, which is the summation order of dS = adj^T G in g4d_spmm_rows_grad_f32 (a defined order: the gradient is reproducible)."""
+    key = (id(adj), str(device))
+    hit = _csr_t_cache.get(key)
+    if hit is not None and hit[0] is adj:
+        return hit[1]
+    mt = _scipy_csr(adj).T.tocsr()
+    mt.sum_duplicates()
+    mt.sort_indices()
+    if len(_csr_t_cache) > 32:
+        _csr_t_cache.clear()
+    csr = _csr_tensors(mt, device)
+    _csr_t_cache[key] = (adj, csr)
     return csr
 
 
@@ -177,8 +215,18 @@ class GraphConvolution(torch.nn.Module):
     def forward(self, input, adj, ismlp=False, relu=False):
         """input (B,N,Fin) or (N,Fin); adj sparse (N,N).  ismlp=True skips the aggregation (layers.py:43,51).
         relu=True (extension) fuses the caller's F.relu into the SpMM epilogue."""
-        if torch.is_grad_enabled() and (input.requires_grad or self.weight.requires_grad):
-            raise NotImplementedError("garment4d_amd.gcn.GraphConvolution is forward-only: call it under torch.no_grad()")
+        if torch.is_grad_enabled():
+            on = _T().gcn_autograd
+            if (input.requires_grad or self.weight.requires_grad) and not on:
+                raise NotImplementedError("garment4d_amd.gcn.GraphConvolution is forward-only: call it under torch.no_grad() "
+                                          "(or opt in to the backward kernels: tuning.Tuning.gcn_autograd / G4D_GCN_AUTOGRAD=1)")
+            if on and (input.requires_grad or self.weight.requires_grad or (self.bias is not None and self.bias.requires_grad)):
+                return _layer_autograd(self, input, adj, ismlp, relu, None)
+        return self._forward_launches(input, adj, ismlp, relu, None)
+
+    def _forward_launches(self, input, adj, ismlp, relu, in_width):
+        """The layer's launches (no autograd graph).  in_width: see gcn_stack_forward -- `input` carries zero columns behind its first
+        in_width = in_features ones and the contraction runs over the padded rows with a zero-padded weight (the same bits)."""
         if not (input.is_cuda and input.dtype == torch.float32):
             raise RuntimeError("GraphConvolution: input must be a float32 HIP tensor")
         x = input.contiguous()
@@ -187,6 +235,9 @@ class GraphConvolution(torch.nn.Module):
         if squeeze:
             x = x.unsqueeze(0)
         B, N, Fin = x.shape
+        if in_width is not None and Fin != in_width:
+            assert not ismlp, "a padded input is the stack's first layer, which aggregates"
+            L_support = self._packed_support_padded(Fin)
         out = torch.empty((B, N, self.out_features), dtype=torch.float32, device=x.device)
         if ismlp:
             # layers.py:43: `support` only gets the bias when one exists -- same thing here (shift = bias or 0)
@@ -202,8 +253,85 @@ class GraphConvolution(torch.nn.Module):
             out.clamp_(min=0)
         return out[0] if squeeze else out
 
+    def _packed_transposed(self):
+        """W itself as the "transposed weight" of a contraction over Cout: dX = dS . W^T through g4d_linear_f32 (K = Cout, Cout = Fin)."""
+        key = (self.weight.data_ptr(), _lib.ver(self.weight))
+        hit = getattr(self, "_g4d_packed_t", None)
+        if hit is None or hit[0] != key:
+            with torch.no_grad():
+                dev = self.weight.device
+                hit = (key, PackedLayer(self.weight.detach().float().contiguous(), torch.ones(self.in_features, device=dev),
+                                        torch.zeros(self.in_features, device=dev), relu=False))
+            self._g4d_packed_t = hit
+        return hit[1]
+
     def __repr__(self):
         return f"{self.__class__.__name__} ({self.in_features} -> {self.out_features})"
+
+
+class _GCNLayerFn(torch.autograd.Function):
+    """One GCN layer Y = act(Ahat (X W) + b) with the backward kernels of csrc/gcn_grad.hip.  forward = GraphConvolution._forward_launches (the
+    inference route's launches and bits); saved: X, W, and Y only when the ReLU is fused (its mask is Y > 0)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, layer, adj, ismlp, relu, in_width):
+        y = layer._forward_launches(x, adj, ismlp, relu, in_width)
+        ctx.layer, ctx.adj, ctx.ismlp, ctx.relu = layer, adj, bool(ismlp), bool(relu)
+        ctx.save_for_backward(x, weight, y if relu else None)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, weight, y = ctx.saved_tensors
+        layer = ctx.layer
+        need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        B, N, ldx = x.shape
+        fin, cout = layer.in_features, layer.out_features
+        rows = B * N
+        dev, stream = x.device, _lib.stream_ptr()
+        dy = dy.contiguous()
+        if dy.dtype != torch.float32:
+            dy = dy.float()
+        yp = y.data_ptr() if y is not None else 0
+        dx = dw = db = None
+        if need_b:   # column sums of G
+            db = torch.empty(cout, dtype=torch.float32, device=dev)
+            ws = torch.empty(max(int(_lib.lib().g4d_col_sum_rows_ws_bytes(rows, cout)) // 4, 1), dtype=torch.float32, device=dev)
+            _lib.call("g4d_col_sum_rows_f32", rows, cout, dy.data_ptr(), yp, ws.data_ptr(), db.data_ptr(), stream)
+        if need_x or need_w:
+            if ctx.ismlp:    # no aggregation: dS = G
+                ds = dy if y is None else torch.where(y > 0, dy, torch.zeros((), dtype=torch.float32, device=dev))
+            else:            # dS = Ahat^T G, the mask applied where dY is loaded
+                rowptr_t, colidx_t, vals_t, n = _to_csr_t(ctx.adj, dev)
+                assert n == N
+                ds = torch.empty((B, N, cout), dtype=torch.float32, device=dev)
+                _lib.call("g4d_spmm_rows_grad_f32", B, N, cout, dy.data_ptr(), yp, rowptr_t.data_ptr(), colidx_t.data_ptr(), vals_t.data_ptr(),
+                          ds.data_ptr(), stream)
+            if need_w:       # dW = X^T dS over the first `fin` columns of the (possibly padded) rows
+                dw = torch.empty((fin, cout), dtype=torch.float32, device=dev)
+                ws = torch.empty(max(int(_lib.lib().g4d_gemm_tn_ws_bytes(rows, fin, cout)) // 4, 1), dtype=torch.float32, device=dev)
+                _lib.call("g4d_gemm_tn_f32", rows, fin, ldx, cout, x.data_ptr(), ds.data_ptr(), ws.data_ptr(), dw.data_ptr(), stream)
+                if dw.dtype != weight.dtype:
+                    dw = dw.to(weight.dtype)
+            if need_x:       # dX = dS W^T; the zero columns of a padded input get zero gradient
+                if ldx == fin:
+                    dx = linear(ds.view(rows, cout), layer._packed_transposed()).view(B, N, fin)
+                else:
+                    dx = torch.zeros((B, N, ldx), dtype=torch.float32, device=dev)
+                    dx[..., :fin] = linear(ds.view(rows, cout), layer._packed_transposed()).view(B, N, fin)
+        return dx, dw, db, None, None, None, None, None
+
+
+def _layer_autograd(layer, input, adj, ismlp, relu, in_width):
+    if not (input.is_cuda and input.dtype == torch.float32):
+        raise RuntimeError("GraphConvolution: input must be a float32 HIP tensor")
+    x = input.contiguous()
+    squeeze = x.dim() == 2
+    if squeeze:
+        x = x.unsqueeze(0)
+    y = _GCNLayerFn.apply(x, layer.weight, layer.bias, layer, adj, ismlp, relu, in_width)
+    return y[0] if squeeze else y
 
 
 # (FUSE_STACK -> tuning.Tuning.gcn_fuse_stack)
@@ -224,8 +352,19 @@ def gcn_stack_forward(layers, x, adj, relu_last=False, keep=(), in_width=None):
     outs = [None] * n
     if not (x.is_cuda and x.dtype == torch.float32):
         raise RuntimeError("gcn_stack_forward: input must be a float32 HIP tensor")
-    if torch.is_grad_enabled() and (x.requires_grad or any(m.weight.requires_grad for m in layers)):
-        raise NotImplementedError("gcn_stack_forward is forward-only: call it under torch.no_grad()")
+    grad_in = torch.is_grad_enabled() and (x.requires_grad or any(m.weight.requires_grad for m in layers))
+    if grad_in or (torch.is_grad_enabled() and _T().gcn_autograd and any(m.bias is not None and m.bias.requires_grad for m in layers)):
+        if not _T().gcn_autograd:
+            raise NotImplementedError("gcn_stack_forward is forward-only: call it under torch.no_grad() "
+                                      "(or opt in to the backward kernels: tuning.Tuning.gcn_autograd / G4D_GCN_AUTOGRAD=1)")
+        # the per-layer autograd functions, chained (the fused aggregate+contract launches below keep h_i in LDS: an inference route)
+        if in_width is not None:
+            assert in_width == layers[0].in_features and x.shape[-1] >= in_width, "in_width must be the first layer's input width"
+        h = x
+        for i, m in enumerate(layers):
+            h = _layer_autograd(m, h, adj, False, i + 1 < n or relu_last, in_width if i == 0 else None)
+            outs[i] = h if (i in keep or i + 1 == n) else None
+        return outs
 
     def fusable(i):   # aggregation of layer i + contraction of layer i + 1
         return (_T().gcn_fuse_stack and i + 1 < n and layers[i].out_features == 128

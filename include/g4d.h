@@ -31,7 +31,7 @@ typedef struct ihipStream_t *g4d_stream_t; /* == hipStream_t */
 #define G4D_OK 0
 #define G4D_EINVAL 10001 /* bad argument (negative size, null pointer, unsupported width) */
 
-int g4d_version(void); /* 100 * major + minor: 200 = round 2 (the `boxes` scratch of g4d_ball_query_boxes_f32 grew to 16-point sub-blocks); 205 / 206 = round 5 (entry points added, none changed; 206: g4d_gcn_tile_meta_*, g4d_gcn_agg_linear_meta_f32); 260 = round 6 (added: g4d_mlp_run / g4d_mlp_args, g4d_mlp_chain_group_table_ws_f32, g4d_sa_table_ws_bytes, g4d_sa_table_supported; none changed); 261 (entry points added, none changed: g4d_mgn_skin_f32) */
+int g4d_version(void); /* 100 * major + minor: 200 = round 2 (the `boxes` scratch of g4d_ball_query_boxes_f32 grew to 16-point sub-blocks); 205 / 206 = round 5 (entry points added, none changed; 206: g4d_gcn_tile_meta_*, g4d_gcn_agg_linear_meta_f32); 260 = round 6 (added: g4d_mlp_run / g4d_mlp_args, g4d_mlp_chain_group_table_ws_f32, g4d_sa_table_ws_bytes, g4d_sa_table_supported; none changed); 261 (entry points added, none changed: g4d_mgn_skin_f32); 262 (entry points added, none changed: g4d_spmm_rows_grad_f32, g4d_col_sum_rows_f32, g4d_gemm_tn_f32 and their size queries) */
 const char *g4d_last_error(void);
 
 /* ---- numerics: how the squared distance of FPS / ball query / three_nn / knn is rounded ---------------------------------
@@ -363,6 +363,30 @@ int g4d_gcn_tile_meta_build(int vg, const int *rowptr, const int *colidx, const 
 int g4d_gcn_agg_linear_meta_f32(int frames, int vg, int c, const float *S, const int *rowptr, const int *colidx, const float *vals,
                                 const float *bias, int relu, float *tap, const float *Wp, int cout, float *out, const void *meta,
                                 g4d_stream_t stream);
+
+/* ---- backward of the GCN layer  Y = act(Ahat . (X W) + b)  (csrc/gcn_grad.hip); rows = frames * Vg, everything point-major ----------
+ * With G = dY where act is the identity and G = (Y > 0 ? dY : 0) where it is the fused ReLU (Y = the layer's OUTPUT; G is never stored):
+ *   dS = Ahat^T . G   g4d_spmm_rows_grad_f32        db = column sums of G   g4d_col_sum_rows_f32
+ *   dW = X^T . dS     g4d_gemm_tn_f32               dX = dS . W^T           g4d_linear_f32 with W as the (Cout = Fin, K = Cout) weight
+ * All three are deterministic (no atomics; partial sums per row slice, added in a fixed order that depends on the shape only). */
+
+/* dS (frames,Vg,C) = Ahat^T . G per frame.  rowptr_t / colidx_t / vals_t: the CSR of Ahat^T (row u lists the v with Ahat[v,u] != 0; the
+ * order of a row's entries is the summation order).  Y == NULL: no mask (G = dY).  One thread per 4 channels of a row, as g4d_spmm_rows_f32. */
+int g4d_spmm_rows_grad_f32(int frames, int vg, int c, const float *dY, const float *Y, const int *rowptr_t, const int *colidx_t,
+                           const float *vals_t, float *dS, g4d_stream_t stream);
+
+/* db (C) = sum over the rows of G (rows,C); Y == NULL: no mask.  ws: g4d_col_sum_rows_ws_bytes(rows, c) bytes.  rows == 0 writes zeros. */
+long long g4d_col_sum_rows_ws_bytes(long long rows, int c);
+int g4d_col_sum_rows_f32(long long rows, int c, const float *dY, const float *Y, float *ws, float *db, g4d_stream_t stream);
+
+/* dW (Fin,Cout) = X^T . dS with X (rows, Fin) of row stride ldx >= Fin floats and dS (rows, Cout) dense: the contraction runs along the
+ * ROWS, on the fp32 matrix cores (v_mfma_f32_32x32x2_f32, the row as k; neither tensor is transposed or padded).  The rows are cut into
+ * slices of g4d_gemm_tn_slice_rows(rows, Fin, Cout) rows -- a function of the shape alone -- whose partial tiles go to ws
+ * (g4d_gemm_tn_ws_bytes bytes) and are then added in slice order.  Any Fin, Cout >= 1; X and dS are read once when Cout <= 128 and Fin
+ * is 128, 193..224 or 321..352 (the model's 128 / 195 / 323), otherwise dS once per 128 features.  rows == 0 writes zeros. */
+long long g4d_gemm_tn_slice_rows(long long rows, int fin, int cout);
+long long g4d_gemm_tn_ws_bytes(long long rows, int fin, int cout);
+int g4d_gemm_tn_f32(long long rows, int fin, int ldx, int cout, const float *X, const float *dS, float *ws, float *dW, g4d_stream_t stream);
 
 /* max (is_max=1) / mean over S consecutive rows, any S: in (groups*S, ldi) -> out (groups, ldo) at col0. */
 int g4d_pool_rows_f32(int groups, int s, int c, const float *in, int ldi, float *out, int ldo, int col0, int is_max,
