@@ -117,7 +117,7 @@ extern "C" int g4d_tuning_set_thread(const char *key, long long value, int set) 
     return G4D_EINVAL;
 }
 
-extern "C" int g4d_version(void) { return 262; /* 262: g4d_spmm_rows_grad_f32, g4d_col_sum_rows_f32, g4d_gemm_tn_f32 (+ size queries) added, none changed; 261: g4d_mgn_skin_f32 added, none changed; 260 = round 6: g4d_mlp_run / g4d_mlp_args, g4d_mlp_chain_group_table_ws_f32 + g4d_sa_table_ws_bytes / _supported (include/g4d.h); 206: round 2 */ }
+extern "C" int g4d_version(void) { return 263; /* 263: g4d_pos_encode_grad_f32, g4d_temporal_attention_grad_f32 (+ size queries) added, none changed; 262: g4d_spmm_rows_grad_f32, g4d_col_sum_rows_f32, g4d_gemm_tn_f32 (+ size queries) added, none changed; 261: g4d_mgn_skin_f32 added, none changed; 260 = round 6: g4d_mlp_run / g4d_mlp_args, g4d_mlp_chain_group_table_ws_f32 + g4d_sa_table_ws_bytes / _supported (include/g4d.h); 206: round 2 */ }
 extern "C" const char *g4d_last_error(void) { return g4d::g_err; }
 
 extern "C" int g4d_get_distance_contraction(void) { return g4d::distance_contraction(); }

@@ -16,6 +16,8 @@ from typing import List, Tuple
 import torch
 import torch.distributed as dist
 
+from .tuning import current as _T
+
 
 def shard_range(n_items: int, rank: int, world: int) -> Tuple[int, int]:
     """Contiguous [begin, end) block of `n_items` for `rank`; sizes differ by at most one."""
@@ -129,8 +131,49 @@ def clip_max_over_frames(frame_feats_local: torch.Tensor, frame_ids_local: torch
     return out
 
 
+class _TemporalAttentionFn(torch.autograd.Function):
+    """qkv Linear + g4d_temporal_attention_f32 (the inference launches and bits); backward: g4d_temporal_attention_grad_f32 for d qkv, then
+    the Linear closes over kernels that exist: dW = d qkv^T x (g4d_gemm_tn_f32), dx = d qkv W (g4d_linear_f32 with the transposed weight).
+    Saved: x, qkv and the (clips, T, T) attention matrix the forward writes anyway."""
+
+    @staticmethod
+    def forward(ctx, x, weight, qkv, T):
+        from . import _lib
+        F_, Vg, C = x.shape
+        n_clips = F_ // T
+        qkv_all = qkv(x).contiguous()
+        res = torch.empty((F_, Vg, C), dtype=torch.float32, device=x.device)
+        scratch = torch.empty(_lib.lib().g4d_temporal_attention_scratch_floats(n_clips, Vg, C), dtype=torch.float32, device=x.device)
+        att = torch.empty((n_clips, T, T), dtype=torch.float32, device=x.device)
+        _lib.call("g4d_temporal_attention_f32", n_clips, T, Vg, C, qkv_all.data_ptr(), scratch.data_ptr(), att.data_ptr(), res.data_ptr(), C, 0,
+                  _lib.stream_ptr())
+        ctx.T = T
+        ctx.save_for_backward(x, weight, qkv_all, att)
+        return res
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        from . import _lib, refine
+        x, weight, qkv_all, att = ctx.saved_tensors
+        F_, Vg, C = x.shape
+        T = ctx.T
+        n_clips, rows = F_ // T, F_ * Vg
+        dout, ldg = refine._grad_window(dout, C)
+        dqkv = torch.empty_like(qkv_all)
+        scratch = torch.empty(_lib.lib().g4d_temporal_attention_grad_scratch_floats(n_clips, Vg, C), dtype=torch.float32, device=x.device)
+        _lib.call("g4d_temporal_attention_grad_f32", n_clips, T, Vg, C, qkv_all.data_ptr(), att.data_ptr(), dout.data_ptr(), ldg, 0, scratch.data_ptr(),
+                  dqkv.data_ptr(), _lib.stream_ptr())
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dx = refine._linear_t(dqkv.view(rows, 3 * C), weight).view(F_, Vg, C)
+        if ctx.needs_input_grad[1]:
+            dw = refine._gemm_tn(rows, C, 3 * C, x, dqkv).t().to(weight.dtype)
+        return dx, dw, None, None
+
+
 def temporal_attention(last_feat_local: torch.Tensor, frame_ids_local: torch.Tensor, n_frames: int, T: int, qkv,
-                       group=None, out=None, col0: int = 0, clip_range=None, gathered: "GatherHandle" = None) -> torch.Tensor:
+                       group=None, out=None, col0: int = 0, clip_range=None, gathered: "GatherHandle" = None, qkv_linear=None) -> torch.Tensor:
     """The reference's temporal attention (mesh_encoder.py:467-476) for frame-sharded features: k, v of ALL T frames
     of a clip are needed, so the per-frame features are all-gathered once (RCCL all-gather; only when `group` names a process
     group, see resolve_group), q/k/v are computed locally, and each rank keeps the rows of its own frames.
@@ -139,7 +182,19 @@ def temporal_attention(last_feat_local: torch.Tensor, frame_ids_local: torch.Ten
     (T <= 32, C % 16 == 0); on CPU tensors (the gloo tests) with torch.matmul.
     out/col0: optional (f_local, Vg, >= col0 + C) buffer to write the result into.
     clip_range = (first, last) clip touched by the local frames (host ints): when sharded, q/k/v and the attention are
-    evaluated for those clips only instead of for every clip of the batch on every rank."""
+    evaluated for those clips only instead of for every clip of the batch on every rank.
+    Training (opt-in: tuning.Tuning.refine_autograd): under grad, with `qkv_linear` = the bias-free nn.Linear behind `qkv`, the call runs as a
+    torch.autograd.Function over the same launches with csrc/attention_grad.hip as its backward and returns the (F, Vg, C) block; a process
+    group then raises NotImplementedError (frame-sharded runs stay inference-only)."""
+    if torch.is_grad_enabled() and _T().refine_autograd and (last_feat_local.requires_grad or (qkv_linear is not None and qkv_linear.weight.requires_grad)):
+        if group is not None and group is not False:
+            raise NotImplementedError("temporal_attention: frame-sharded runs (group=...) are inference-only")
+        if qkv_linear is None or out is not None:
+            raise NotImplementedError("temporal_attention under grad needs qkv_linear= (the nn.Linear behind qkv) and returns its block (no out=)")
+        F_, Vg, C = last_feat_local.shape
+        if not (last_feat_local.is_cuda and T <= 32 and C % 16 == 0 and F_ % T == 0 and qkv_linear.bias is None):
+            raise NotImplementedError(f"temporal_attention backward: needs a HIP tensor, T <= 32, C % 16 == 0, whole clips, a bias-free Linear (T {T}, C {C}, F {F_})")
+        return _TemporalAttentionFn.apply(last_feat_local.contiguous(), qkv_linear.weight, qkv, T)
     sharded = resolve_group(group) is not None
     if sharded:  # `gathered`: the caller started the all-gather earlier so that it overlaps independent work (SURVEY.md 8e)
         feats = gathered.wait() if gathered is not None else allgather_frames(last_feat_local, n_frames, group)

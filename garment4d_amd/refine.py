@@ -7,7 +7,9 @@ Per round: 3 body + 3 garment positional encoders (ball query -> grouped [xyz-of
 -> max over the samples: ONE fused MFMA stack launch each, written straight into its 32-column slot of the GCN input),
 temporal attention over the T frames of a clip (rounds 1, 2), four GCN layers, residual update of the vertices.
 Frame sharding: pass `group` + `frame_ids`; the only exchange is the all-gather inside dist.temporal_attention.
-Inference only.  SURVEY.md section 8f rank 1 -- parity unpinned (mesh_encoder.py cannot be imported here), checked
+Inference by default.  Opt-in training (tuning.Tuning.refine_autograd, environment G4D_REFINE_AUTOGRAD): under grad the head builds an
+autograd graph whose forward launches are the inference route's (the same bits) and whose backward runs csrc/pos_encode_grad.hip,
+csrc/attention_grad.hip and the GCN kernels of csrc/gcn_grad.hip; frame-sharded runs stay inference-only.  SURVEY.md section 8f rank 1 -- parity unpinned (mesh_encoder.py cannot be imported here), checked
 against oracle/refine_oracle.py."""
 import torch
 import torch.nn as nn
@@ -15,6 +17,7 @@ import torch.nn as nn
 from . import _lib
 from . import dist as gdist
 from . import fused
+from . import tuning as _tuning
 from .tuning import current as _T
 from .gcn import GraphConvolution, gcn_stack_forward
 
@@ -97,7 +100,7 @@ def _pe_kernel_weights(seq, n_in):
     return hit[1]
 
 
-def positional_encoding(mlp, radius, nsample, xyz, new_xyz, feats_pm, out, col0, idx=None, table=None):
+def positional_encoding(mlp, radius, nsample, xyz, new_xyz, feats_pm, out, col0, idx=None, table=None, _kernel_only=False):
     """QueryAndGroup(radius, nsample, use_xyz=True) -> mlp -> max over samples, into out[..., col0:col0+Cout].
     xyz (F,N,3) cloud, new_xyz (F,Vg,3) queries, feats_pm (F,N,C) point-major.  idx: precomputed ball query;
     table: precomputed per-source-point first-layer feature part (see _split_first_linear) for wide features.
@@ -109,7 +112,8 @@ def positional_encoding(mlp, radius, nsample, xyz, new_xyz, feats_pm, out, col0,
     Vg = new_xyz.shape[1]
     C = feats_pm.shape[2]
     n_extra = 0 if table is not None else C
-    w = _pe_kernel_weights(mlp, 3 + n_extra) if (_T().use_pe_kernel and nsample in (4, 8, 16, 32, 64) and n_extra <= 5) else None
+    w = _pe_kernel_weights(mlp, 3 + n_extra) if ((_T().use_pe_kernel or _kernel_only) and nsample in (4, 8, 16, 32, 64) and n_extra <= 5) else None
+    assert w is not None or not _kernel_only
     if w is not None:
         W1, b1, W2f, b2 = w
         _lib.call("g4d_pos_encode_f32", F_, N, Vg, nsample, n_extra, xyz.data_ptr(), new_xyz.data_ptr(),
@@ -126,6 +130,130 @@ def feature_table(mlp, feats_pm):
     t = _split_first_linear(mlp)[0]
     F_, N, C = feats_pm.shape
     return fused.linear(feats_pm.reshape(F_ * N, C), t).view(F_, N, -1)
+
+
+# ---------------------------------------------------------------------------------------------------------------- training route (opt-in)
+def _grad_window(g, width):
+    """A cotangent (F, V, width) as (tensor, leading dimension): the column window of a wider row-major buffer (what the backward of
+    torch.cat hands over) is read in place through its row stride; anything else is made contiguous."""
+    if g.dtype != torch.float32:
+        g = g.float()
+    F_, V, _ = g.shape
+    if g.stride(2) == 1 and g.stride(1) >= width and g.stride(0) == V * g.stride(1):
+        return g, g.stride(1)
+    return g.contiguous(), width
+
+
+def _col_sum(rows, c, x):
+    out = torch.empty(c, dtype=torch.float32, device=x.device)
+    ws = torch.empty(max(int(_lib.lib().g4d_col_sum_rows_ws_bytes(rows, c)) // 4, 1), dtype=torch.float32, device=x.device)
+    _lib.call("g4d_col_sum_rows_f32", rows, c, x.data_ptr(), 0, ws.data_ptr(), out.data_ptr(), _lib.stream_ptr())
+    return out
+
+
+def _gemm_tn(rows, fin, cout, x, ds):
+    """X^T dS (fin, cout) over `rows` rows: g4d_gemm_tn_f32, slice partials added in a fixed order."""
+    dw = torch.empty((fin, cout), dtype=torch.float32, device=x.device)
+    ws = torch.empty(max(int(_lib.lib().g4d_gemm_tn_ws_bytes(rows, fin, cout)) // 4, 1), dtype=torch.float32, device=x.device)
+    _lib.call("g4d_gemm_tn_f32", rows, fin, fin, cout, x.data_ptr(), ds.data_ptr(), ws.data_ptr(), dw.data_ptr(), _lib.stream_ptr())
+    return dw
+
+
+def _linear_t(ds2d, weight):
+    """dS . W for a Linear weight W (Cout, Cin): g4d_linear_f32 with W^T as the packed (Cin x Cout-deep) layer."""
+    cin = weight.shape[1]
+    with torch.no_grad():
+        L = fused.PackedLayer(weight.detach().float().t().contiguous(), torch.ones(cin, device=weight.device),
+                              torch.zeros(cin, device=weight.device), relu=False)
+    return fused.linear(ds2d, L)
+
+
+class _FeatureTableFn(torch.autograd.Function):
+    """G = Wf f + b1 per source point (feature_table: the same launch and bits); backward over kernels that exist: dWf = dG^T f
+    (g4d_gemm_tn_f32), db1 = column sums of dG (g4d_col_sum_rows_f32), df = dG Wf (g4d_linear_f32)."""
+
+    @staticmethod
+    def forward(ctx, feats, Wf, b1, mlp):
+        ctx.save_for_backward(feats, Wf)
+        return feature_table(mlp, feats)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dG):
+        feats, Wf = ctx.saved_tensors
+        F_, N, C = feats.shape
+        rows, H = F_ * N, Wf.shape[0]
+        dG = dG.contiguous().float()
+        df = dWf = db = None
+        if ctx.needs_input_grad[0]:
+            df = _linear_t(dG.view(rows, H), Wf).view(F_, N, C)
+        if ctx.needs_input_grad[1]:
+            dWf = _gemm_tn(rows, C, H, feats, dG).t().to(Wf.dtype)
+        if ctx.needs_input_grad[2]:
+            db = _col_sum(rows, H, dG)
+        return df, dWf, db, None
+
+
+class _PosEncodeFn(torch.autograd.Function):
+    """One positional encoder on g4d_pos_encode_f32 (the inference launch) with g4d_pos_encode_grad_f32 as its backward.  W1 is the part of
+    the first Linear the kernel contracts ((32, 3 + n_extra); with a table its xyz columns), b1 None with a table.  The ball-query
+    indices are constants of the graph, as in the reference's QueryAndGroup."""
+
+    @staticmethod
+    def forward(ctx, new_xyz, xyz, extra, table, W1, b1, W2, b2, mlp, idx, nsample):
+        F_, N, _ = xyz.shape
+        Vg = new_xyz.shape[1]
+        n_extra = 0 if table is not None else (0 if extra is None else extra.shape[2])
+        out = torch.empty((F_, Vg, 32), dtype=torch.float32, device=xyz.device)
+        positional_encoding(mlp, None, nsample, xyz, new_xyz, extra if extra is not None else xyz[..., :0], out, 0, idx=idx, table=table, _kernel_only=True)
+        ctx.dims = (F_, N, Vg, nsample, n_extra)
+        ctx.save_for_backward(new_xyz, xyz, extra, table, idx, W1, W2, b1)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        new_xyz, xyz, extra, table, idx, W1, W2, b1 = ctx.saved_tensors
+        F_, N, Vg, S, n_extra = ctx.dims
+        dev = xyz.device
+        need = ctx.needs_input_grad
+        dout, ldg = _grad_window(dout, 32)
+        W1c, W2c = W1.detach().float().contiguous(), W2.detach().float().contiguous()
+        f32 = dict(dtype=torch.float32, device=dev)
+        d_new = torch.empty((F_, Vg, 3), **f32) if need[0] else None
+        d_xyz = torch.zeros((F_, N, 3), **f32) if need[1] else None
+        d_extra = torch.zeros((F_, N, n_extra), **f32) if (need[2] and n_extra) else None
+        d_table = torch.zeros((F_, N, 32), **f32) if (need[3] and table is not None) else None
+        dW1 = torch.empty((32, 3 + n_extra), **f32) if need[4] else None
+        db1 = torch.empty(32, **f32) if (need[5] and table is None) else None
+        dW2 = torch.empty((32, 32), **f32) if need[6] else None
+        db2 = torch.empty(32, **f32) if need[7] else None
+        ws = None
+        if dW1 is not None or db1 is not None or dW2 is not None or db2 is not None:
+            ws = torch.empty(max(int(_lib.lib().g4d_pos_encode_grad_ws_bytes(F_, Vg, S)) // 4, 1), **f32)
+        P = lambda t: 0 if t is None else t.data_ptr()
+        b1c = None if table is not None else b1.detach().float().contiguous()   # with a table the bias sits in the table (NULL, as in the forward)
+        _lib.call("g4d_pos_encode_grad_f32", F_, N, Vg, S, n_extra, xyz.data_ptr(), new_xyz.data_ptr(), P(extra) if n_extra else 0, P(table),
+                  idx.data_ptr(), W1c.data_ptr(), P(b1c), W2c.data_ptr(), dout.data_ptr(), ldg, 0, P(ws), P(dW1), P(db1), P(dW2), P(db2), P(d_new),
+                  P(d_xyz), P(d_extra), P(d_table), _lib.stream_ptr())
+        return d_new, d_xyz, d_extra, d_table, dW1, db1, dW2, db2, None, None, None
+
+
+def _positional_encoding_autograd(mlp, nsample, xyz, new_xyz, feats_pm, idx, table):
+    """The training route of positional_encoding: returns the (F, Vg, 32) block (the caller concatenates).  Only the dedicated kernel's
+    shape domain has a backward."""
+    C = feats_pm.shape[2]
+    n_extra = 0 if table is not None else C
+    ok = nsample in (4, 8, 16, 32, 64) and n_extra <= 5 and _pe_kernel_weights(mlp, 3 + n_extra) is not None and new_xyz.shape[1] * nsample >= 64
+    if not ok:
+        raise NotImplementedError(f"positional encoder backward: only the dedicated kernel's shapes (hidden = out = 32, nsample in 4|8|16|32|64, "
+                                  f"at most 5 extra columns or a table) -- got nsample {nsample}, {C} feature columns, table {table is not None}, "
+                                  f"mlp {mlp}")
+    lin0, lin2 = mlp[0], mlp[2]
+    xyz, new_xyz, feats_pm = xyz.contiguous(), new_xyz.contiguous(), feats_pm.contiguous()
+    if table is not None:
+        return _PosEncodeFn.apply(new_xyz, xyz, None, table, lin0.weight[:, :3], None, lin2.weight, lin2.bias, mlp, idx, nsample)
+    return _PosEncodeFn.apply(new_xyz, xyz, feats_pm if n_extra else None, None, lin0.weight, lin0.bias, lin2.weight, lin2.bias, mlp, idx, nsample)
 
 
 class GarmentRefinementHead(nn.Module):
@@ -178,7 +306,10 @@ class GarmentRefinementHead(nn.Module):
         and garment_f_list[i] (F,N_i,C_i) POINT-major encoder levels; adj the normalised garment adjacency; F = local frames
         (= nbatch*T without sharding; with sharding pass the process group and the global ids of the local frames).
         Returns the list of refined vertices per round (mesh_encoder.py:485)."""
-        assert not torch.is_grad_enabled(), "GarmentRefinementHead is inference-only: call under torch.no_grad()"
+        if torch.is_grad_enabled() and _T().refine_autograd:
+            return self._forward_autograd(cur_garment_v, body_v, body_vn, garment_v_list, garment_f_list, adj, nbatch, T, group)
+        assert not torch.is_grad_enabled(), ("GarmentRefinementHead is inference-only: call under torch.no_grad() (or opt in to the backward "
+                                             "kernels: tuning.Tuning.refine_autograd / G4D_REFINE_AUTOGRAD=1)")
         body_pe = [self.body_positional_encoding0, self.body_positional_encoding1, self.body_positional_encoding2]
         garm_pe = [self.garment_positional_encoding0, self.garment_positional_encoding1, self.garment_positional_encoding2]
         qkvs = [self.temporal_qkv_1, self.temporal_qkv_2]
@@ -226,4 +357,57 @@ class GarmentRefinementHead(nn.Module):
                 pending = gdist.allgather_frames_async(hs[2], n_frames, group)
             cur = (cur + h).contiguous()                                             # :482-483
             outs.append(cur)
+        return outs
+
+    def _forward_autograd(self, cur_garment_v, body_v, body_vn, garment_v_list, garment_f_list, adj, nbatch, T, group):
+        """The training route (tuning.Tuning.refine_autograd): the same launches as the inference route -- so every round's output has the same
+        bits -- inside torch.autograd.Functions, the column slots of the GCN input replaced by one torch.cat per round.  Gradients reach every
+        parameter of the head, cur_garment_v (direct copy, residual and every x_j - q) and garment_v_list[i] / garment_f_list[i] when they
+        require grad; body_v / body_vn are constants; the ball-query indices are constants of the graph (the reference's QueryAndGroup)."""
+        if group is not None and group is not False:
+            raise NotImplementedError("GarmentRefinementHead: frame-sharded runs (group=...) are inference-only; train with whole clips per rank")
+        body_pe = [self.body_positional_encoding0, self.body_positional_encoding1, self.body_positional_encoding2]
+        garm_pe = [self.garment_positional_encoding0, self.garment_positional_encoding1, self.garment_positional_encoding2]
+        qkvs = [self.temporal_qkv_1, self.temporal_qkv_2]
+        regress = [self.lbs_graph_regress1, self.lbs_graph_regress2, self.lbs_graph_regress3]
+        F_, Vg, _ = cur_garment_v.shape
+        dev = cur_garment_v.device
+        n_frames = nbatch * T
+        assert F_ == n_frames, "the training route takes whole clips: F = nbatch * T frames"
+        frame_ids = torch.arange(F_, device=dev)
+        body_v, body_vn = body_v.detach().contiguous(), body_vn.detach().contiguous()
+        gv = [v.contiguous() for v in garment_v_list]
+        gf = [f.contiguous() for f in garment_f_list]
+        cur = cur_garment_v.contiguous()
+        outs, lbs_iter_feat = [], []
+        tables = []
+        for i in range(3):
+            if gf[i].shape[2] > self.feat_num:
+                lin0 = garm_pe[i][0]
+                tables.append(_FeatureTableFn.apply(gf[i], lin0.weight[:, 3:], lin0.bias, garm_pe[i]))
+            else:
+                tables.append(None)
+        with _tuning.use(_T().replace(gcn_autograd=True)):
+            for it in range(self.iteration):
+                width = self.graph_start_feature_dim + (self.hidden_dim if it > 0 else 0)
+                wpad = (width + 3) // 4 * 4
+                with torch.no_grad():
+                    body_idx = fused.ball_query_msg(self.body_radius_list, self.body_sample_num_list, body_v, cur.detach(), coherent=True)
+                    garm_idx = [fused.ball_query_msg([self.garment_radius_list[i]], [self.garment_sample_num_list[i]], gv[i].detach(), cur.detach())[0]
+                                for i in range(3)]
+                blocks = [cur]
+                for i in range(3):
+                    blocks.append(_positional_encoding_autograd(body_pe[i], self.body_sample_num_list[i], body_v, cur, body_vn, body_idx[i], None))
+                for i in range(3):
+                    blocks.append(_positional_encoding_autograd(garm_pe[i], self.garment_sample_num_list[i], gv[i], cur, gf[i], garm_idx[i], tables[i]))
+                if it > 0:
+                    blocks.append(gdist.temporal_attention(lbs_iter_feat[-2], frame_ids, n_frames, T, self._qkv(qkvs[it - 1]), None,
+                                                           qkv_linear=qkvs[it - 1]))
+                if wpad > width:
+                    blocks.append(torch.zeros((F_, Vg, wpad - width), dtype=torch.float32, device=dev))
+                feat = torch.cat(blocks, dim=-1)
+                hs = gcn_stack_forward(regress[it], feat, adj, relu_last=False, keep=(2,), in_width=width)
+                lbs_iter_feat += hs
+                cur = (cur + hs[-1]).contiguous()
+                outs.append(cur)
         return outs

@@ -83,6 +83,9 @@ class Tuning:
     gcn_fuse_stack: bool = True        # gcn.py: fused GCN stack launches
     gcn_autograd: bool = False         # gcn.py: a grad-requiring GraphConvolution / gcn_stack_forward call builds an autograd graph over the backward
                                        #  kernels of csrc/gcn_grad.hip (False: such a call raises NotImplementedError, as it always did)
+    refine_autograd: bool = False      # refine.py: GarmentRefinementHead.forward under grad builds an autograd graph over csrc/pos_encode_grad.hip,
+                                       #  csrc/attention_grad.hip and the GCN route above (which it implies for the layers inside the head); False: such
+                                       #  a call raises AssertionError, as it always did
     # ---- lbs() routes (lbs.py).  NOT bit-identical to each other (different partitions of the blend sum; each within 1e-5 of the reference)
     lbs_fused: bool = True             # False: the five-step path that follows smplx/lbs.py line by line
     lbs_mfma: bool = True              # round 5: matrix-pipe route (g4d_lbs_mfma_f32), taken at every batch size
@@ -122,6 +125,7 @@ def from_environment() -> Tuning:
         fp_wide_fused=_env_flag("G4D_FP_WIDE_FUSED", d.fp_wide_fused), fp_cells=_env_flag("G4D_FP_CELLS", d.fp_cells), fp_table=_env_flag("G4D_FP_TABLE", d.fp_table),
         fp_gemm_bf16=_env_flag("G4D_FP_GEMM_BF16", d.fp_gemm_bf16), fp_gemm_bf16_min_rows=_env_int("G4D_FP_GEMM_BF16_MIN_ROWS", d.fp_gemm_bf16_min_rows),
         fp_wide_table=_env_flag("G4D_FP_WIDE_TABLE", d.fp_wide_table), gcn_fuse_stack=_env_flag("G4D_GCN_FUSED", d.gcn_fuse_stack), gcn_autograd=_env_flag("G4D_GCN_AUTOGRAD", d.gcn_autograd),
+        refine_autograd=_env_flag("G4D_REFINE_AUTOGRAD", d.refine_autograd),
         dropin_fused=_env_flag("G4D_DROPIN_FUSED", d.dropin_fused), dropin_whole_model=_env_flag("G4D_DROPIN_WHOLE", d.dropin_whole_model), lbs_mfma=_env_flag("G4D_LBS_MFMA", d.lbs_mfma), lbs_one_launch=_env_flag("G4D_LBS_ONE", d.lbs_one_launch),
         lbs_one_launch_max_b=_env_int("G4D_LBS_ONE_MAX_B", d.lbs_one_launch_max_b))
 

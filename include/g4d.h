@@ -31,7 +31,7 @@ typedef struct ihipStream_t *g4d_stream_t; /* == hipStream_t */
 #define G4D_OK 0
 #define G4D_EINVAL 10001 /* bad argument (negative size, null pointer, unsupported width) */
 
-int g4d_version(void); /* 100 * major + minor: 200 = round 2 (the `boxes` scratch of g4d_ball_query_boxes_f32 grew to 16-point sub-blocks); 205 / 206 = round 5 (entry points added, none changed; 206: g4d_gcn_tile_meta_*, g4d_gcn_agg_linear_meta_f32); 260 = round 6 (added: g4d_mlp_run / g4d_mlp_args, g4d_mlp_chain_group_table_ws_f32, g4d_sa_table_ws_bytes, g4d_sa_table_supported; none changed); 261 (entry points added, none changed: g4d_mgn_skin_f32); 262 (entry points added, none changed: g4d_spmm_rows_grad_f32, g4d_col_sum_rows_f32, g4d_gemm_tn_f32 and their size queries) */
+int g4d_version(void); /* 100 * major + minor: 200 = round 2 (the `boxes` scratch of g4d_ball_query_boxes_f32 grew to 16-point sub-blocks); 205 / 206 = round 5 (entry points added, none changed; 206: g4d_gcn_tile_meta_*, g4d_gcn_agg_linear_meta_f32); 260 = round 6 (added: g4d_mlp_run / g4d_mlp_args, g4d_mlp_chain_group_table_ws_f32, g4d_sa_table_ws_bytes, g4d_sa_table_supported; none changed); 261 (entry points added, none changed: g4d_mgn_skin_f32); 262 (entry points added, none changed: g4d_spmm_rows_grad_f32, g4d_col_sum_rows_f32, g4d_gemm_tn_f32 and their size queries); 263 (entry points added, none changed: g4d_pos_encode_grad_f32, g4d_temporal_attention_grad_f32 and their size queries) */
 const char *g4d_last_error(void);
 
 /* ---- numerics: how the squared distance of FPS / ball query / three_nn / knn is rounded ---------------------------------
@@ -701,6 +701,29 @@ int g4d_pos_encode_f32(int frames, int n, int p, int nsample, int n_extra, const
 size_t g4d_temporal_attention_scratch_floats(int nclips, int vg, int c);
 int g4d_temporal_attention_f32(int nclips, int t, int vg, int c, const float *qkv, float *scratch, float *att, float *out, int ldo,
                                int col0, g4d_stream_t stream);
+
+/* Backward of g4d_pos_encode_f32 (same shape domain, same operands; W2 here is the second Linear's weight ROW-MAJOR (32,32), not in fragment
+ * order).  dOut: the gradient of the encoder's 32 output columns, read at dOut[(f*p + q)*ldg + col0 .. +32).  The forward is recomputed per
+ * query; per channel the gradient goes to the first sample that attains the maximum.  Every output pointer may be NULL ("nobody needs it":
+ * its work is skipped):
+ *   dW1 (32, 3+n_extra), db1 (32), dW2 (32,32), db2 (32): written; reduced without atomics (one partial per workgroup in ws, summed in a
+ *     fixed order): bit-reproducible.  ws: g4d_pos_encode_grad_ws_bytes(frames, p, nsample) bytes, needed when any of the four is asked for.
+ *   d_new_xyz (frames,p,3): written, one value per query, no atomics.
+ *   d_xyz (frames,n,3), d_extra (frames,n,n_extra), d_table (frames,n,32): fp32 atomic scatter-ADDS into the source-point rows; the caller
+ *     zero-fills them (or passes a buffer to accumulate into).  With a table, db1 is the caller's column sum of d_table. */
+long long g4d_pos_encode_grad_ws_bytes(int frames, int p, int nsample);
+int g4d_pos_encode_grad_f32(int frames, int n, int p, int nsample, int n_extra, const float *xyz, const float *new_xyz,
+                            const float *extra, const float *table, const int *idx, const float *W1, const float *b1,
+                            const float *W2, const float *dOut, int ldg, int col0, float *ws, float *dW1, float *db1, float *dW2,
+                            float *db2, float *d_new_xyz, float *d_xyz, float *d_extra, float *d_table, g4d_stream_t stream);
+
+/* Backward of g4d_temporal_attention_f32: qkv and att as the forward read / wrote them, dO the gradient of its output read at
+ * dO[((clip*t + frame)*vg + vertex)*ldg + col0 .. +c);  dqkv (nclips*t, vg, 3c) = [dQ | dK | dV] in the layout of qkv, fully written.
+ * dA = dO V^T, dS = A (dA - rowsum(dA A)) / sqrt(t), dQ = dS K, dK = dS^T Q, dV = A^T dO.  No atomics: bit-reproducible.
+ * scratch: g4d_temporal_attention_grad_scratch_floats(nclips, vg, c) floats. */
+size_t g4d_temporal_attention_grad_scratch_floats(int nclips, int vg, int c);
+int g4d_temporal_attention_grad_f32(int nclips, int t, int vg, int c, const float *qkv, const float *att, const float *dO, int ldg,
+                                    int col0, float *scratch, float *dqkv, g4d_stream_t stream);
 
 /* Ordered per-frame compaction of `calc_segmentation_results` (modules/mesh_encoder.py:109-125): sel (frames,n_out) = the
  * indices k (ascending) of the points whose arg-max over `classes` logits (first maximum wins) equals `target`, the
