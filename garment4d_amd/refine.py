@@ -105,14 +105,16 @@ def positional_encoding(mlp, radius, nsample, xyz, new_xyz, feats_pm, out, col0,
     xyz (F,N,3) cloud, new_xyz (F,Vg,3) queries, feats_pm (F,N,C) point-major.  idx: precomputed ball query;
     table: precomputed per-source-point first-layer feature part (see _split_first_linear) for wide features.
     The reference's shapes (hidden = out = 32, nsample a power of two <= 64, C <= 5 or a table) run on the dedicated
-    wave-autonomous kernel (csrc/pos_encode.hip); anything else on the generic fused stack."""
+    wave-autonomous kernel (csrc/pos_encode.hip); anything else on the generic fused stack -- also a frame of fewer than 64 grouped rows
+    (Vg * nsample < 64: a wave's 64-row chunk would span more than two frames, the launcher refuses it)."""
     if idx is None:
         idx = fused.ball_query_msg([radius], [nsample], xyz, new_xyz)[0]
     F_, N, _ = xyz.shape
     Vg = new_xyz.shape[1]
     C = feats_pm.shape[2]
     n_extra = 0 if table is not None else C
-    w = _pe_kernel_weights(mlp, 3 + n_extra) if ((_T().use_pe_kernel or _kernel_only) and nsample in (4, 8, 16, 32, 64) and n_extra <= 5) else None
+    w = _pe_kernel_weights(mlp, 3 + n_extra) if ((_T().use_pe_kernel or _kernel_only) and nsample in (4, 8, 16, 32, 64) and n_extra <= 5
+                                                 and Vg * nsample >= 64) else None
     assert w is not None or not _kernel_only
     if w is not None:
         W1, b1, W2f, b2 = w

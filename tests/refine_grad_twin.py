@@ -1,6 +1,8 @@
 """float64 twin of the two operators the refinement head's training route adds -- the positional encoder (csrc/pos_encode_grad.hip) and the
 temporal attention (csrc/attention_grad.hip) -- in dense numpy, shared by tests/test_refine_grad_cpu.py (which ties it to the reference's own
-autograd through tests/golden/refine_grad.npz) and tests/test_refine_grad_gpu.py (which holds the HIP kernels to it).  Not a test module.
+autograd through tests/golden/refine_grad.npz) and tests/test_refine_grad_gpu.py (which holds the HIP kernels to it); the forward of the
+positional encoder (csrc/pos_encode.hip) is held to pe_forward within pe_forward_bound by tests/test_pos_encode_cpu.py (the oracle) and
+tests/test_pos_encode_gpu.py (the kernel and the generic route).  Not a test module.
 
 Positional encoder, per query q with samples s and source point j_s = idx[q, s]:
     in_s = [x_j - q ; e_j]   z1_s = W1 in_s + (b1 | t_j)   h_s = relu(z1_s)   z2_s = W2 h_s   out[c] = max_s z2_s[c] + b2[c]
@@ -31,7 +33,8 @@ def load():
 
 def pe_forward(xyz, new_xyz, extra, table, idx, W1, b1, W2, b2):
     """All float64.  xyz (F,N,3), new_xyz (F,P,3), extra (F,N,E) or None, table (F,N,32) or None, idx (F,P,S).  Returns a dict with the grouped
-    input `inp` (F,P,S,KX), z1, h, z2, out, the winning sample `win` (F,P,32) and hA."""
+    input `inp` (F,P,S,KX), z1, h, z2, out, the winning sample `win` (F,P,32), hA (masked by z1 > 0: the yardstick of the gradients) and
+    hA_full (unmasked: the yardstick of the forward, see pe_forward_bound)."""
     f64 = lambda a: None if a is None else np.asarray(a, dtype=np.float64)
     xyz, new_xyz, extra, table, W1, b1, W2, b2 = map(f64, (xyz, new_xyz, extra, table, W1, b1, W2, b2))
     F_, P, S = idx.shape
@@ -50,7 +53,113 @@ def pe_forward(xyz, new_xyz, extra, table, idx, W1, b1, W2, b2):
     z2 = h @ W2.T
     win = np.argmax(z2, axis=2)                                  # (F,P,32), first maximum
     out = np.take_along_axis(z2, win[:, :, None, :], 2)[:, :, 0, :] + b2
-    return dict(inp=inp, z1=z1, h=h, hA=hA * (z1 > 0), z2=z2, out=out, win=win, idx=ix)
+    return dict(inp=inp, z1=z1, h=h, hA=hA * (z1 > 0), hA_full=hA, z2=z2, out=out, win=win, idx=ix)
+
+
+def pe_forward_bound(fw, W2, b2, table_err=None):
+    """(F,P,32): first-order bound of |fp32 forward - fw["out"]|, per output element
+        max over the S rows of (32 + KX + 5) u (|W2| hA_full)  +  u (|out| + |b2|),           hA_full = |t| + |b1| + |W1| |in|.
+    Derivation (the rule of the module header: a sum of n products with m roundings of their own errs by at most (n + m) u A):
+      * layer 1, z1 = (t | b1) + W1 in: KX products, the bias / table addition and the rounding of the coordinate difference, which every
+        implementation forms first in fp32: |dz1| <= (KX + 3) u hA_full.  hA_full is NOT masked by the sign of z1: a row whose float64
+        pre-activation is slightly negative may be slightly positive in fp32, and its error still counts;
+      * |relu(a) - relu(b)| <= |a - b|, so h inherits the error of z1, and |h| <= hA_full;
+      * layer 2, z2 = W2 h: 32 products of inexact h: |dz2| <= |W2| |dz1| + (32 + 2) u |W2| |h| <= (32 + KX + 5) u |W2| hA_full;
+      * |max_s a_s - max_s b_s| <= max_s |a_s - b_s|: the pooled value errs by at most the largest row error of its query;
+      * out = max + b2: one more rounding, u (|out| + |b2|) bounds it to first order.
+    table_err (F,N,32), optional: the absolute error of the TABLE's entries where the fp32 table was itself computed (table_forward); it
+    enters layer 1's error term per source point and is carried through |W2| like the rest.  Nothing here is a measured number."""
+    W2a, b2 = np.abs(np.asarray(W2, np.float64)), np.asarray(b2, np.float64)
+    hA, ix = fw["hA_full"], fw["idx"]
+    kx = fw["inp"].shape[-1]
+    e1 = (kx + 3) * U * hA
+    if table_err is not None:
+        e1 = e1 + np.asarray(table_err, np.float64)[np.arange(ix.shape[0])[:, None, None], ix]
+    e2 = e1 @ W2a.T + (32 + 2) * U * (hA @ W2a.T)                  # (F,P,S,32)
+    return e2.max(axis=2) + U * (np.abs(fw["out"]) + np.abs(b2))
+
+
+def table_forward(feats, Wf, b1):
+    """The per-source-point first-layer table t = Wf f + b1 (refine.feature_table) in float64, and the bound of an fp32 evaluation's error:
+    C products plus the bias addition, (C + 2) u (|Wf| |f| + |b1|) with C the width of the Linear the table is split from (its three
+    coordinate columns counted too: a looser count than the C - 3 products the table contracts, never a tighter one)."""
+    feats, Wf, b1 = (np.asarray(a, np.float64) for a in (feats, Wf, b1))
+    C = Wf.shape[1] + 3
+    return feats @ Wf.T + b1, (C + 2) * U * (np.abs(feats) @ np.abs(Wf).T + np.abs(b1))
+
+
+def pe_case(seed, F_, N, P, S, E, table, hits=None):
+    """Synthetic encoder inputs.  idx: per query `hits` distinct source points (1 .. S; default uniform in 1 .. S), then copies of the first
+    hit -- the shape of a ball query's output."""
+    rng = np.random.default_rng(seed)
+    c = dict(F=F_, N=N, P=P, S=S, E=E)
+    c["xyz"] = rng.standard_normal((F_, N, 3)).astype(np.float32)
+    c["new_xyz"] = rng.standard_normal((F_, P, 3)).astype(np.float32)
+    c["extra"] = rng.standard_normal((F_, N, E)).astype(np.float32) if E else None
+    c["table"] = (rng.standard_normal((F_, N, 32)) * 0.5).astype(np.float32) if table else None
+    idx = rng.integers(0, N, (F_, P, S)).astype(np.int32)
+    nh = rng.integers(1, S + 1, (F_, P)) if hits is None else np.minimum(rng.integers(1, hits + 1, (F_, P)), S)
+    idx = np.where(np.arange(S)[None, None, :] < nh[..., None], idx, idx[..., :1])
+    c["idx"] = idx
+    c["W1"] = (rng.uniform(-1, 1, (32, 3 + E)) / np.sqrt(3 + E)).astype(np.float32)
+    c["b1"] = None if table else rng.uniform(-0.3, 0.3, 32).astype(np.float32)
+    c["W2"] = (rng.uniform(-1, 1, (32, 32)) / np.sqrt(32)).astype(np.float32)
+    c["b2"] = rng.uniform(-0.3, 0.3, 32).astype(np.float32)
+    c["dOut"] = rng.standard_normal((F_, P, 32)).astype(np.float32)
+    return c
+
+
+def _distinct_rows(rng, rows, cols, lo=-2, hi=2):
+    """An integer matrix with entries in [lo, hi] whose rows are pairwise distinct (drawn without replacement among the base-(hi-lo+1) codes)."""
+    base = hi - lo + 1
+    codes = rng.choice(base ** min(cols, 12), rows, replace=False)
+    m = np.stack([(codes // base ** i) % base for i in range(min(cols, 12))], 1) + lo
+    if cols > 12:
+        m = np.concatenate([m, rng.integers(lo, hi + 1, (rows, cols - 12))], 1)
+    return m.astype(np.float32)
+
+
+def pe_exact_case(seed, F_, N, P, S, E, table, hits=None):
+    """pe_case with integer-valued operands small enough that every partial sum of the forward is an integer below 2^24, whatever its order:
+    coordinates in [-4, 4], extras in [-3, 3], W1 / W2 entries in [-2, 2], biases and table entries in [-8, 8]
+    (|z1| <= 8 + 2 (3 x 8 + 5 x 3) = 86, |z2| <= 32 x 2 x 86 = 5504).  fp32 and float64 then agree bit for bit.  W1 and W2 have pairwise distinct
+    rows and columns and W2 is not symmetric, so a permuted channel, a wrong k-step or a neighbour's sample changes the result."""
+    rng = np.random.default_rng(seed)
+    c = pe_case(seed, F_, N, P, S, E, table, hits=hits)
+    ints = lambda lo, hi, shape: rng.integers(lo, hi + 1, shape).astype(np.float32)
+    c["xyz"], c["new_xyz"] = ints(-4, 4, (F_, N, 3)), ints(-4, 4, (F_, P, 3))
+    c["extra"] = ints(-3, 3, (F_, N, E)) if E else None
+    c["table"] = ints(-8, 8, (F_, N, 32)) if table else None
+    c["W1"], c["W2"] = _distinct_rows(rng, 32, 3 + E), _distinct_rows(rng, 32, 32)
+    c["b1"] = None if table else ints(-8, 8, 32)
+    c["b2"] = ints(-8, 8, 32)
+    for w in (c["W1"], c["W2"]):
+        assert len({tuple(r) for r in w}) == 32 and len({tuple(r) for r in w.T}) == w.shape[1], "rows / columns must be pairwise distinct"
+    assert not np.array_equal(c["W2"], c["W2"].T)
+    return c
+
+
+def pe_exact_expected(c):
+    """The float64 output of an exact case, with the checks that make it one: every sum stays below 2^24 and the result is not degenerate
+    (more than half of the entries differ from b2, i.e. the ReLU did not kill everything)."""
+    fw = pe_forward(c["xyz"], c["new_xyz"], c["extra"], c["table"], c["idx"], c["W1"], c["b1"], c["W2"], c["b2"])
+    assert np.abs(fw["z2"]).max() + np.abs(c["b2"]).max() < 2.0 ** 24 and (np.abs(fw["hA_full"]) @ np.abs(c["W2"]).T.astype(np.float64)).max() < 2.0 ** 24
+    assert np.array_equal(fw["out"], np.rint(fw["out"]))
+    assert (fw["out"] != c["b2"].astype(np.float64)).mean() > 0.5, "degenerate expected output: change the draw"
+    return fw["out"]
+
+
+def pe_twin(c, frames=None, table_err=None):
+    """(out, bound) of a pe_case-shaped dict in float64, frame by frame so that a full-size launch fits; `frames`: only these (default all)."""
+    frames = range(c["F"]) if frames is None else frames
+    outs, bnds = [], []
+    for f in frames:
+        s = slice(f, f + 1)
+        fw = pe_forward(c["xyz"][s], c["new_xyz"][s], None if c["extra"] is None else c["extra"][s], None if c["table"] is None else c["table"][s],
+                        c["idx"][s], c["W1"], c["b1"], c["W2"], c["b2"])
+        outs.append(fw["out"])
+        bnds.append(pe_forward_bound(fw, c["W2"], c["b2"], None if table_err is None else table_err[s]))
+    return np.concatenate(outs, 0), np.concatenate(bnds, 0)
 
 
 def pe_flags(fw, margin):

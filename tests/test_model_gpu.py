@@ -88,19 +88,22 @@ def test_segment_points_vs_oracle(frac):
     assert np.array_equal(counts.cpu().numpy(), (np.argmax(logits, 2) == 6).sum(1))
 
 
-@pytest.mark.parametrize("garment,lbs_k,size", [("Tshirt", 64, "small"), ("Trousers", 3, "small"), ("Tshirt", 256, "cfg4"), ("Tshirt", 256, "cfg4_T30")])
+@pytest.mark.parametrize("garment,lbs_k,size", [("Tshirt", 64, "small"), ("Trousers", 3, "small"), ("Tshirt", 256, "cfg4"), ("Tshirt", 256, "cfg4_T30"),
+                                                 ("Tshirt", 64, "small_ragged")])
 def test_full_forward_vs_oracle(garment, lbs_k, size):
     """size "cfg4": BASELINE config 4's per-frame sizes -- N = 8192 points, 6890 body vertices, 4096 garment vertices, K = 256 -- for one
     4-frame clip: the kernel instantiations of the benched model (bucketed FPS, cell-grid ball query, K = 256 radix-select KNN,
     LDS-resident 100-step smoothing, sub-block body ball query, windowed fused GCN launches) against the numpy restatement.
     "cfg4_T30": the same sizes for one FULL 30-frame clip -- T is the dimension of the temporal attention (a T x T soft-max over
-    Vg * C = 524288-long rows) and of the clip max of the garment summary."""
+    Vg * C = 524288-long rows) and of the clip max of the garment summary.
+    "small_ragged": the small sizes with a 195-vertex garment template (13 x 15): Vg * nsample is no multiple of 64 for any nsample <= 32, so the
+    positional encoders' 64-row chunks straddle frames."""
     if size.startswith("cfg4"):
         nbatch, T, N = 1, (30 if size == "cfg4_T30" else 4), 8192
         scene = syn.garment_scene(nbatch, T, N, body_rc=(65, 106), garment_rc=(64, 64), seed=11)
     else:
         nbatch, T, N = 2, 3, 2048
-        scene = syn.garment_scene(nbatch, T, N, seed=11)
+        scene = syn.garment_scene(nbatch, T, N, seed=11, **({"garment_rc": (13, 15)} if size == "small_ragged" else {}))
     m = _model(scene, garment, lbs_k)
     sd = {k: v.detach().cpu().numpy() for k, v in m.state_dict().items()}
     with torch.no_grad():

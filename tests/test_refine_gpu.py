@@ -16,10 +16,13 @@ def dev(a):
     return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
-def _case(nbatch, T, V=700, seed=0, garment="Tshirt"):
+RAGGED = (13, 15)   # 195 garment vertices: 195 * nsample is no multiple of 64 for any nsample <= 32, so the positional encoders' 64-row chunks straddle frames
+
+
+def _case(nbatch, T, V=700, seed=0, garment="Tshirt", rc=(12, 16)):
     rng = np.random.default_rng(seed)
     F_ = nbatch * T
-    verts, faces = syn.quad_cylinder(12, 16)
+    verts, faces = syn.quad_cylinder(*rc)
     Vg = verts.shape[0]
     body_v = (syn.unit_cloud(F_, V, seed=seed + 1) - 0.5).astype(np.float32) * 0.8
     body_vn = rng.standard_normal((F_, V, 3)).astype(np.float32)
@@ -72,6 +75,35 @@ def test_first_round_vs_oracle(garment, pe_kernel, tune):
     np.testing.assert_allclose(got[0].cpu().numpy(), want[0], rtol=1e-5, atol=1e-5)   # measured: 1e-7
 
 
+@pytest.mark.parametrize("pe_kernel", [True, False])
+@pytest.mark.parametrize("garment", ["Tshirt", "Trousers"])
+def test_first_round_vs_oracle_ragged_mesh(garment, pe_kernel, tune):
+    """The same gate on a 195-vertex mesh.  The first round queries bit-identical points on both sides: no ball-membership flip can occur."""
+    tune(use_pe_kernel=pe_kernel)
+    nbatch, T = 2, 3
+    head, sd, cur, body_v, body_vn, gv, gf, adj = _case(nbatch, T, seed=3, garment=garment, rc=RAGGED)
+    assert cur.shape[1] == 195 and all((195 * s) % 64 for s in (4, 8, 16, 32))
+    head.iteration = 1
+    got = _run(head, cur, body_v, body_vn, gv, gf, adj, nbatch, T)
+    want = RO.refinement_head(sd, cur, body_v, body_vn, gv, gf, adj, nbatch, T, garment_samples=tuple(head.garment_sample_num_list),
+                              iteration=1)
+    assert len(got) == 1
+    np.testing.assert_allclose(got[0].cpu().numpy(), want[0], rtol=1e-5, atol=1e-5)
+
+
+def test_first_round_vs_oracle_six_vertex_mesh():
+    """quad_cylinder(2, 3): 6 * 8 = 48 grouped rows per frame go to the generic stack (fewer than one 64-row chunk), 6 * 16 and 6 * 32 to the
+    dedicated kernel."""
+    nbatch, T = 2, 3
+    head, sd, cur, body_v, body_vn, gv, gf, adj = _case(nbatch, T, seed=3, rc=(2, 3))
+    assert cur.shape[1] == 6
+    head.iteration = 1
+    got = _run(head, cur, body_v, body_vn, gv, gf, adj, nbatch, T)
+    want = RO.refinement_head(sd, cur, body_v, body_vn, gv, gf, adj, nbatch, T, garment_samples=tuple(head.garment_sample_num_list),
+                              iteration=1)
+    np.testing.assert_allclose(got[0].cpu().numpy(), want[0], rtol=1e-5, atol=1e-5)
+
+
 def membership_flips(got_prev, want_idx, body_v, gv, body_samples, garment_samples, radii=(0.1, 0.2, 0.4)):
     """Per frame: how many of the round's 6 x Vg ball queries return a different index row on the GPU (queries = the GPU's own
     previous-round vertices) than in the oracle (its own previous-round vertices).  The two vertex sets differ by fp32 rounding,
@@ -87,12 +119,12 @@ def membership_flips(got_prev, want_idx, body_v, gv, body_samples, garment_sampl
     return flips
 
 
-def test_three_rounds_vs_oracle():
+def _three_rounds_vs_oracle(seed, rc):
     """Rounds 2 and 3 re-query the balls around vertices that differ by rounding between the two implementations.  Frames whose
     queries all return the oracle's rows (and whose clip had none flipped in an earlier round: the attention mixes a clip's
     frames) must agree to a MAXIMUM error bound; flipped queries are counted and must be rare."""
     nbatch, T = 2, 3
-    head, sd, cur, body_v, body_vn, gv, gf, adj = _case(nbatch, T, seed=5)
+    head, sd, cur, body_v, body_vn, gv, gf, adj = _case(nbatch, T, seed=seed, rc=rc)
     got = _run(head, cur, body_v, body_vn, gv, gf, adj, nbatch, T)
     want, want_idx = RO.refinement_head(sd, cur, body_v, body_vn, gv, gf, adj, nbatch, T, return_ball_idx=True)
     assert len(got) == 3
@@ -112,6 +144,15 @@ def test_three_rounds_vs_oracle():
         assert err[clean].max() <= 1e-5 * scale, (r, err, flips)   # measured: 1.2e-7 with no flip on this seed
         dirty_clip |= (flips.reshape(nbatch, T) > 0).any(1)
     assert total_flips <= 1e-3 * 2 * 6 * Vg * nbatch * T, total_flips
+
+
+def test_three_rounds_vs_oracle():
+    _three_rounds_vs_oracle(5, (12, 16))
+
+
+def test_three_rounds_vs_oracle_ragged_mesh():
+    """The same protocol and caps on the 195-vertex mesh."""
+    _three_rounds_vs_oracle(5, RAGGED)
 
 
 def test_attention_only_mixes_frames_of_a_clip():

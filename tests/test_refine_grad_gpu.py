@@ -36,25 +36,7 @@ def refine_on():
 
 
 # ---- positional encoder -------------------------------------------------------------------------------------------------------------------
-def pe_case(seed, F_, N, P, S, E, table, hits=None):
-    """Synthetic encoder inputs.  idx: per query `hits` distinct source points (1 .. S; default uniform in 1 .. S), then copies of the first
-    hit -- the shape of a ball query's output."""
-    rng = np.random.default_rng(seed)
-    c = dict(F=F_, N=N, P=P, S=S, E=E)
-    c["xyz"] = rng.standard_normal((F_, N, 3)).astype(np.float32)
-    c["new_xyz"] = rng.standard_normal((F_, P, 3)).astype(np.float32)
-    c["extra"] = rng.standard_normal((F_, N, E)).astype(np.float32) if E else None
-    c["table"] = (rng.standard_normal((F_, N, 32)) * 0.5).astype(np.float32) if table else None
-    idx = rng.integers(0, N, (F_, P, S)).astype(np.int32)
-    nh = rng.integers(1, S + 1, (F_, P)) if hits is None else np.minimum(rng.integers(1, hits + 1, (F_, P)), S)
-    idx = np.where(np.arange(S)[None, None, :] < nh[..., None], idx, idx[..., :1])
-    c["idx"] = idx
-    c["W1"] = (rng.uniform(-1, 1, (32, 3 + E)) / np.sqrt(3 + E)).astype(np.float32)
-    c["b1"] = None if table else rng.uniform(-0.3, 0.3, 32).astype(np.float32)
-    c["W2"] = (rng.uniform(-1, 1, (32, 32)) / np.sqrt(32)).astype(np.float32)
-    c["b2"] = rng.uniform(-0.3, 0.3, 32).astype(np.float32)
-    c["dOut"] = rng.standard_normal((F_, P, 32)).astype(np.float32)
-    return c
+pe_case = TW.pe_case   # shared with tests/test_pos_encode_gpu.py
 
 
 def hip_pe_grad(c, dOut, ldg=32, col0=0, want=PE_OUTPUTS):
@@ -275,6 +257,38 @@ def test_head_trains_under_the_switch(golden_refine):
         assert t.grad is not None and t.grad.shape == t.shape and torch.isfinite(t.grad).all() and t.grad.abs().max() > 0, name
     with pytest.raises(AssertionError):    # and off again outside the block
         head(cur, body_v, body_vn, gv, gf, adj, nbatch, T)
+
+
+def test_training_route_forward_bits_on_a_ragged_mesh():
+    """195 garment vertices (13 x 15): the positional encoders' 64-row chunks straddle frames; the training route's forward is still the
+    inference route's, bit for bit."""
+    rng = np.random.default_rng(31)
+    nbatch, T, V = 2, 3, 700
+    F_ = nbatch * T
+    verts, faces = syn.quad_cylinder(13, 15)
+    Vg = verts.shape[0]
+    assert Vg == 195 and all((Vg * s) % 64 for s in (4, 8, 16, 32))
+    body_v = dev((syn.unit_cloud(F_, V, seed=32) - 0.5).astype(np.float32) * 0.8)
+    body_vn = torch.nn.functional.normalize(torch.from_numpy(rng.standard_normal((F_, V, 3)).astype(np.float32)), dim=-1).cuda()
+    cur = (body_v[:, torch.from_numpy(rng.permutation(V)[:Vg]).cuda()] + dev(rng.standard_normal((F_, Vg, 3)).astype(np.float32)) * 0.03).contiguous()
+    gv, gf = [], []
+    for n, c in ((512, 64), (128, 96), (32, 384)):
+        sel = torch.from_numpy(rng.integers(0, Vg, n)).cuda()
+        gv.append((cur[:, sel] + dev(rng.standard_normal((F_, n, 3)).astype(np.float32)) * 0.05).contiguous())
+        gf.append(dev(rng.standard_normal((F_, n, c)).astype(np.float32)))
+    adj = G.sparse_mx_to_torch_sparse_tensor(GO.adjacency_from_faces(faces, Vg)).cuda()
+    torch.manual_seed(31)
+    head = GarmentRefinementHead(garment_name="Tshirt").cuda().eval()
+    with torch.no_grad():
+        for p in head.parameters():
+            p.mul_(0.5)
+        want = head(cur, body_v, body_vn, gv, gf, adj, nbatch, T)
+    cur.requires_grad_(True)
+    with refine_on():
+        outs = head(cur, body_v, body_vn, gv, gf, adj, nbatch, T)
+    assert len(outs) == len(want) == 3 and outs[-1].requires_grad
+    for a, b in zip(outs, want):
+        assert torch.equal(a.detach(), b), "the training route's forward is the inference route's bits"
 
 
 def test_generic_encoder_shapes_have_no_backward():
