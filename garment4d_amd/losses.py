@@ -1,7 +1,9 @@
-"""Evaluation-side helpers that share the kernels of the hot path, forward only:
-`calc_interpenetration_loss` (smplx/loss/temporal_loss.py:20-46) = vertex normals + nearest body vertex +
+"""Losses that share the kernels of the hot path.
+`calc_interpenetration_loss` (smplx/loss/temporal_loss.py:20-46), forward only = vertex normals + nearest body vertex +
 penalty, each on a HIP kernel.  The nearest vertex comes from the three-nearest-neighbour kernel of the feature-propagation
-layers (ties -> lowest index, like knn_points here), not from a K=1 top-K search."""
+layers (ties -> lowest index, like knn_points here), not from a K=1 top-K search.
+`temporal_loss_PCA_LBS` (:147-201), the stage-2 objective of the refinement head, with its analytic gradient w.r.t. the round outputs
+(csrc/refine_loss.hip); `stage2_loss` is the same on plain tensors."""
 import numpy as np
 import torch
 
@@ -46,3 +48,182 @@ def calc_interpenetration_loss(body_model, so, garment_v, reduce_fn="sum", to_ro
     if reduce_fn == "mean":
         return pen.mean()
     raise NotImplementedError
+
+
+# ------------------------------------------------------------------------------------------------------------ the stage-2 objective
+# `temporal_loss_PCA_LBS` (smplx/loss/temporal_loss.py:147-201): the function whose total_loss.backward() trains the refinement head in the
+# reference's second stage (train_temporal.py --fix_PCA).  Values and dL/d(round output) come from csrc/refine_loss.hip, one call per round;
+# what is in front of the rounds (targets, body, normals, the nearest-vertex index) is constant, as in the reference.
+LOSS_LAMBDAS = ("LBS_GARMENT_L2_LOSS_LAMBDA", "LBS_GARMENT_LAP_LOSS_LAMBDA", "LBS_INTERPENETRATION_LOSS_LAMBDA", "TEMPORAL_CONSTRAINT_LOSS_LAMBDA")
+_lap_cache = {}
+
+
+def laplacian_csr(lap_adj, device):
+    """The operands of g4d_refine_loss_f32 for the mesh Laplacian `lap_adj` (the model's output_dict['lap_adj'], a torch sparse (Vg, Vg)
+    tensor, or a scipy sparse matrix): (rowptr, colidx, vals, rowsum, rowptr_t, colidx_t, vals_t), i.e. the CSR of L, its row sums (float64
+    sums of the fp32 entries) and the CSR of L^T (L's pattern on a symmetric mesh, values -1/deg of the OTHER vertex), all on `device`.
+    Recovered from the matrix itself -- whatever the caller built it from -- once per object (cached by identity, like
+    garment_lbs._smoothing_csr): scipy work and seven host-to-device copies, which do not belong inside a hipGraph capture."""
+    key = (id(lap_adj), str(device))
+    hit = _lap_cache.get(key)
+    if hit is not None and hit[0] is lap_adj:
+        return hit[1]
+    assert not torch.cuda.is_current_stream_capturing(), "laplacian_csr: build the operator before the capture (call the loss once eagerly)"
+    import scipy.sparse as sp
+    if torch.is_tensor(lap_adj):
+        c = lap_adj.detach().coalesce() if lap_adj.is_sparse else lap_adj.detach().to_sparse().coalesce()
+        ij = c.indices().cpu().numpy()
+        L = sp.csr_matrix((c.values().float().cpu().numpy(), (ij[0], ij[1])), shape=tuple(c.shape))
+    else:
+        L = sp.csr_matrix(lap_adj).astype(np.float32)
+    assert L.shape[0] == L.shape[1], "the Laplacian is square"
+    L.sum_duplicates()
+    L.sort_indices()
+    Lt = sp.csr_matrix(L.T)
+    Lt.sort_indices()
+    rowsum = np.asarray(L.astype(np.float64).sum(1)).reshape(-1).astype(np.float32)
+    dev = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a).astype(dt)).to(device)
+    val = (dev(L.indptr, np.int32), dev(L.indices, np.int32), dev(L.data, np.float32), dev(rowsum, np.float32),
+           dev(Lt.indptr, np.int32), dev(Lt.indices, np.int32), dev(Lt.data, np.float32))
+    if len(_lap_cache) > 8:
+        _lap_cache.clear()
+    _lap_cache[key] = (lap_adj, val)
+    return val
+
+
+def _lambdas(loss_cfg):
+    get = (lambda k: loss_cfg[k]) if isinstance(loss_cfg, dict) else (lambda k: getattr(loss_cfg, k))
+    return tuple(float(get(k)) for k in LOSS_LAMBDAS)
+
+
+def _evaluate_rounds(rounds, want, target, body_v, body_vn, csr, nbatch, T, weights):
+    """One g4d_refine_loss_f32 call per round.  Returns (vals (R, 5) = [L2, MSRE, Laplacian, penetration, temporal] per round -- the temporal
+    term evaluated for the last round only --, msre_frames (F) of the last round, [dL/d round or None])."""
+    R = len(rounds)
+    F_, Vg, _ = rounds[0].shape
+    V = body_v.shape[1]
+    dev = body_v.device
+    vals = torch.empty((R, 5), dtype=torch.float32, device=dev)
+    msre = torch.empty((F_,), dtype=torch.float32, device=dev)
+    ws_grad = max(int(_lib.lib().g4d_refine_loss_ws_bytes(F_, Vg, 1)) // 4, 1)
+    ws_vals = max(int(_lib.lib().g4d_refine_loss_ws_bytes(F_, Vg, 0)) // 4, 1)
+    ws = torch.empty(ws_grad if any(want) else ws_vals, dtype=torch.float32, device=dev)   # one workspace: the rounds run in stream order
+    grads = []
+    st = _lib.stream_ptr()
+    for r, p in enumerate(rounds):
+        p = p.detach().float().contiguous()
+        assert p.shape == (F_, Vg, 3), "every round's prediction is (nbatch * T, Vg, 3)"
+        idx = fused.three_nn(p, body_v)[1] if F_ * Vg else torch.zeros((F_, Vg, 3), dtype=torch.int32, device=dev)
+        g = torch.empty_like(p) if want[r] else None
+        last = r == R - 1
+        _lib.call("g4d_refine_loss_f32", nbatch, T, Vg, V, p.data_ptr(), target.data_ptr(), body_v.data_ptr(), body_vn.data_ptr(), idx.data_ptr(), 3,
+                  *[t.data_ptr() for t in csr], weights[0], weights[1], weights[2], weights[3] if last else 0.0, int(last), ws.data_ptr(),
+                  vals[r].data_ptr(), msre.data_ptr() if last else 0, 0 if g is None else g.data_ptr(), st)
+        grads.append(g)
+    return vals, msre, grads
+
+
+def _total(vals, weights):
+    acc = vals.sum(0)
+    return (acc[0] * weights[0] + acc[2] * weights[1] + acc[3] * weights[2]) + vals[-1, 4] * weights[3]
+
+
+class _Stage2LossFn(torch.autograd.Function):
+    """total_loss over the round outputs: the forward evaluates every round and keeps dL/d(round) of those that require grad; the backward
+    hands each its stored gradient times the incoming scalar."""
+
+    @staticmethod
+    def forward(ctx, consts, *rounds):
+        target, body_v, body_vn, csr, nbatch, T, weights = consts
+        want = [bool(n) for n in ctx.needs_input_grad[1:]]
+        vals, msre, grads = _evaluate_rounds(rounds, want, target, body_v, body_vn, csr, nbatch, T, weights)
+        ctx.want = want
+        ctx.save_for_backward(*[g for g in grads if g is not None])
+        ctx.mark_non_differentiable(vals, msre)
+        return _total(vals, weights), vals, msre
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_total, _g_vals, _g_msre):
+        saved = iter(ctx.saved_tensors)
+        return (None,) + tuple((next(saved) * g_total) if w else None for w in ctx.want)
+
+
+def stage2_loss(rounds, target, body_v, body_vn, lap_adj, nbatch, T, weights):
+    """The objective on tensors: rounds = the per-round predictions (F, Vg, 3), F = nbatch * T; target (F, Vg, 3); body_v / body_vn (F, V, 3)
+    body vertices / unit normals; lap_adj the mesh Laplacian (see laplacian_csr); weights = the four lambdas (L2, Laplacian, penetration,
+    temporal).  Returns (total, vals (R, 5), msre_frames (F,)); `total` carries the graph when grad is enabled and a round requires grad,
+    `vals` / `msre_frames` never do.  Without grad: the same launches without gradient buffers, the same bits."""
+    rounds = list(rounds)
+    assert len(rounds) >= 1 and all(p.dim() == 3 and p.shape[-1] == 3 for p in rounds)
+    if torch.is_grad_enabled():
+        for name, t in (("target", target), ("body_v", body_v), ("body_vn", body_vn)):
+            if t.requires_grad:
+                raise NotImplementedError(f"stage-2 loss: {name} requires grad -- only the round outputs are differentiated (targets, body vertices and "
+                                          "normals are constants of the graph, as in the reference's second stage)")
+    dev = rounds[0].device
+    with torch.no_grad():
+        target, body_v, body_vn = (t.detach().to(dev).float().contiguous() for t in (target, body_v, body_vn))
+    F_, Vg, _ = rounds[0].shape
+    assert F_ == nbatch * T and target.shape == (F_, Vg, 3) and body_v.shape == body_vn.shape and body_v.shape[0] == F_
+    csr = laplacian_csr(lap_adj, dev)
+    assert csr[0].numel() == Vg + 1, "lap_adj is (Vg, Vg)"
+    weights = tuple(float(w) for w in weights)
+    if torch.is_grad_enabled() and any(p.requires_grad for p in rounds):
+        return _Stage2LossFn.apply((target, body_v, body_vn, csr, nbatch, T, weights), *rounds)
+    with torch.no_grad():
+        vals, msre, _ = _evaluate_rounds(rounds, [False] * len(rounds), target, body_v, body_vn, csr, nbatch, T, weights)
+        return _total(vals, weights), vals, msre
+
+
+def _acceleration_error(pred, gt, nbatch, T):
+    """calc_acceleration_error (:133-145); an evaluation figure outside total_loss."""
+    def accel(v):
+        v = v.reshape(nbatch, T, -1, 3)
+        vel = (v[:, 1:] - v[:, :-1]) / (1 / 30)
+        return (vel[:, 1:] - vel[:, :-1]) / (1 / 30)
+    return ((accel(pred) - accel(gt)) ** 2).sum(-1).sqrt().mean()
+
+
+def temporal_loss_PCA_LBS(output_dict, inputs, body_model, args=None, *, loss_cfg):
+    """The reference's four positional arguments (`args` is not read) plus loss_cfg: anything with the four LBS_* / TEMPORAL_* lambdas as
+    attributes (cfg.LOSS) or a dict.  Reads output_dict['iter_regressed_lbs_garment_v' | 'lbs_pred_garment_v' | 'lap_adj'] and
+    inputs['pose_torch' | 'smpl_vertices_torch' | 'smpl_root_joints_torch' | 'garment_torch']; returns the reference's loss_dict keys.
+    `total_loss` is differentiable w.r.t. the round outputs (one autograd node on csrc/refine_loss.hip); every other entry is a detached
+    figure.  The Laplacian's CSR is recovered from `lap_adj` itself, once per object (laplacian_csr)."""
+    weights = _lambdas(loss_cfg)
+    rounds = list(output_dict["iter_regressed_lbs_garment_v"])
+    dev = rounds[0].device
+    nbatch, T = inputs["pose_torch"].shape[0], inputs["pose_torch"].shape[1]
+    F_ = nbatch * T
+    if torch.is_grad_enabled():
+        for k in ("garment_torch", "smpl_vertices_torch", "smpl_root_joints_torch"):
+            if inputs[k].requires_grad:
+                raise NotImplementedError(f"temporal_loss_PCA_LBS: inputs['{k}'] requires grad -- only the round outputs are differentiated")
+    with torch.no_grad():
+        body_v = inputs["smpl_vertices_torch"].to(dev).reshape(F_, -1, 3).float().contiguous()
+        joints = inputs["smpl_root_joints_torch"].to(dev).reshape(F_, 1, 3).float()
+        gt = (inputs["garment_torch"].to(dev).reshape(F_, -1, 3).float() + joints[:, 0, :].unsqueeze(1)).contiguous()
+        assert body_model.faces.shape[1] == 3 and body_v.shape[1] >= 3, "body needs triangle faces and >= 3 vertices"
+        key = id(body_model)
+        if key not in _vf:
+            fid, vid = mesh_utils.calc_body_mesh_info(body_model)
+            _vf.clear()
+            _vf[key] = (fid.cuda(), vid.cuda(), torch.from_numpy(np.asarray(body_model.faces).astype(np.int64)).cuda())
+        fid, vid, faces = _vf[key]
+        body_vn = mesh_utils.compute_vnorms(body_v, faces, vid, fid)
+    rounds = [p.reshape(F_, -1, 3) for p in rounds]
+    total, vals, msre = stage2_loss(rounds, gt, body_v, body_vn, output_dict["lap_adj"], nbatch, T, weights)
+    with torch.no_grad():
+        acc = vals.sum(0)
+        lbs_pred = output_dict["lbs_pred_garment_v"].detach().to(dev).reshape(F_, -1, 3).float()
+        last = rounds[-1].detach()
+        return {
+            "lbs_garment_msre": vals[-1, 1], "lbs_garment_msre_list": msre.reshape(nbatch, T),
+            "only_lbs_garment_msre": ((lbs_pred - gt) ** 2).sum(-1).sqrt().mean(),
+            "lbs_garment_l2_loss": acc[0], "lbs_garment_lap_loss": acc[2], "lbs_interpenetration_loss": acc[3],
+            "temporal_constraint_loss": vals[-1, 4],
+            "acceleration_error": _acceleration_error(last, gt, nbatch, T),
+            "only_lbs_acceleration_error": _acceleration_error(lbs_pred, gt, nbatch, T),
+            "total_loss": total,
+        }

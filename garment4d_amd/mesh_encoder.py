@@ -9,7 +9,9 @@ so a reference checkpoint's `state_dict` loads by key:
     {body,garment}_positional_encoding{0,1,2}, temporal_qkv_{1,2}, lbs_graph_regress{1,2,3}     (refine.GarmentRefinementHead)
     displacement_encoder.{0,2,4}                                       MGN variant: Linear 512 -> 1024 -> 2048 -> 3 Vg
 
-Inference only.  What the constructor needs from disk in the reference (the PCA basis pickle
+Inference only -- except PCALBSGarmentUseSegEncoderSeg.forward under grad with tuning.Tuning.refine_autograd
+on: the reference's second training stage (encoder, normals and skinning under no_grad, the refinement head under grad; the objective is
+losses.temporal_loss_PCA_LBS).  What the constructor needs from disk in the reference (the PCA basis pickle
 and the garment template OBJ, both part of the CLOTH3D-derived data set that is not available here) can be given either
 through the reference's cfg (`cfg.GARMENT.PCACOMPONENTSFILE`, `cfg.GARMENT.TEMPLATE`) or as arrays.  Frames may be
 sharded over ranks: pass `group` / `frame_ids`; the exchanges are the clip max of the garment summary (all-reduce MAX of
@@ -26,6 +28,7 @@ from . import dist as gdist
 from . import fused
 from . import gcn
 from . import mesh_utils
+from . import tuning
 from .encoder import Pointnet2MSGSEG
 from .garment_lbs import lbs_garment_interpolation, lbs_garment_MGN
 from .pointnet2_modules import PointnetSAModule, PointnetSAModuleMSG
@@ -199,7 +202,23 @@ class PCALBSGarmentUseSegEncoderSeg(GarmentRefinementHead):
             return self._forward(x, body_model, batch)
 
     def _forward(self, x, body_model, batch):
-        assert not torch.is_grad_enabled() and not _any_training(self), "inference only: model.eval() (every submodule) under torch.no_grad()"
+        # Stage-2 training (opt-in, tuning.Tuning.refine_autograd; the reference's train_temporal.py --fix_PCA): under grad everything in front
+        # of the head runs under torch.no_grad() -- the reference does not differentiate it either (modules/mesh_encoder.py:416-417) -- with
+        # the encoder entirely in eval(), and only GarmentRefinementHead.forward builds a graph.  The head's own modules hold no BatchNorm or
+        # dropout, so their mode does not matter there.  Same launches, same output bits as the inference route.
+        train = torch.is_grad_enabled() and tuning.current().refine_autograd
+        if train:
+            assert not _any_training(self.PCA_garment_encoder), "inference only: model.eval() (every submodule) under torch.no_grad()"
+        else:
+            assert not torch.is_grad_enabled() and not _any_training(self), "inference only: model.eval() (every submodule) under torch.no_grad()"
+        with torch.no_grad():
+            out, cur, body_v, body_vn, nbatch, T = self._front(x, body_model, batch)
+        out["iter_regressed_lbs_garment_v"] = GarmentRefinementHead.forward(
+            self, cur, body_v, body_vn, out["garment_v_list"], out["_garment_f_list_pm"], self._adj_scipy, nbatch, T, group=False)
+        return out
+
+    def _front(self, x, body_model, batch):
+        """Everything in front of the refinement head: encoder, body normals, garment skinning (never differentiated)."""
         import scipy.sparse as sp
         nbatch, T = x.size(0), x.size(1)
         dev = x.device
@@ -220,9 +239,7 @@ class PCALBSGarmentUseSegEncoderSeg(GarmentRefinementHead):
             batch["zeropose_smpl_vertices_torch"].to(dev), body_model, batch["pose_torch"].to(dev), batch["T_J_regressor"].to(dev),
             batch["T_lbs_weights"].to(dev), K=self.lbs_k)
         cur = out["lbs_pred_garment_v"].reshape(nbatch * T, -1, 3).contiguous()
-        out["iter_regressed_lbs_garment_v"] = GarmentRefinementHead.forward(
-            self, cur, body_v, body_vn, out["garment_v_list"], out["_garment_f_list_pm"], self._adj_scipy, nbatch, T, group=False)
-        return out
+        return out, cur, body_v, body_vn, nbatch, T
 
     def forward_frames(self, x, body_model, batch, *, nbatch, T, frame_ids, group=gdist.WORLD):
         """Frame-sharded forward: this rank holds the frames `frame_ids` (ascending global ids, clip =

@@ -209,6 +209,55 @@ def refine_golden_checksum(case):
     return np.array([float(np.asarray(a, dtype=np.float64).sum()) for a in items])
 
 
+def vertex_normals(verts, faces):
+    """Unit vertex normals (F,V,3) float32 of triangle meshes sharing `faces`: unit face normals summed per vertex, re-normalised (float64
+    inside).  Only used to PLACE synthetic garments around a body; the product's normals come from its own kernel."""
+    v = np.asarray(verts, dtype=np.float64)
+    f = np.asarray(faces, dtype=np.int64)
+    fn = np.cross(v[:, f[:, 1]] - v[:, f[:, 0]], v[:, f[:, 2]] - v[:, f[:, 0]])
+    fn /= np.maximum(np.linalg.norm(fn, axis=-1, keepdims=True), 1e-12)
+    vn = np.zeros_like(v)
+    for c in range(3):
+        for fr in range(v.shape[0]):
+            np.add.at(vn[fr], f[:, c], fn[fr])
+    vn /= np.maximum(np.linalg.norm(vn, axis=-1, keepdims=True), 1e-12)
+    return vn.astype(F32)
+
+
+def garment_around_body(rng, body_v, body_n, sel, sigma=0.01, jitter=0.002):
+    """(F,len(sel),3) float32: the body vertices `sel` moved along their normals by N(0, sigma) plus N(0, jitter) per coordinate -- about half
+    of the vertices end up behind the surface, and none sits at rounding distance of it."""
+    F_, n = body_v.shape[0], len(sel)
+    return (body_v[:, sel] + body_n[:, sel] * rng.normal(0.0, sigma, (F_, n, 1)) + rng.normal(0.0, jitter, (F_, n, 3))).astype(F32)
+
+
+def stage2_loss_case(seed=170):
+    """The inputs of tests/golden/stage2_loss.npz (written by tests/golden/make_golden_stage2_loss.py, which runs the reference's own
+    `temporal_loss_PCA_LBS` on them): the body and the 64-vertex quad-cylinder template of refine_golden_case, three leaf rounds and an
+    `lbs_pred_garment_v` placed around the body (garment_around_body; garment vertex i follows body vertex sel[i] in every frame), random
+    `garment_torch` (near the rounds, relative to the root) and random root joints.  stage2_loss_checksum() guards against generator drift."""
+    base = refine_golden_case()
+    nbatch, T, Vg = base["nbatch"], base["T"], base["Vg"]
+    F_ = nbatch * T
+    rng = np.random.default_rng(seed)
+    body_v = base["batch"]["smpl_vertices_torch"].reshape(F_, -1, 3)
+    body_n = vertex_normals(body_v, base["body"]["faces"])
+    sel = rng.permutation(body_v.shape[1])[:Vg]
+    rounds = [garment_around_body(rng, body_v, body_n, sel) for _ in range(3)]
+    lbs_pred = garment_around_body(rng, body_v, body_n, sel)
+    root = rng.normal(0.0, 0.05, (nbatch, T, 3)).astype(F32)
+    garment = (body_v[:, sel] + rng.normal(0.0, 0.01, (F_, Vg, 3))).astype(F32).reshape(nbatch, T, Vg, 3) - root[:, :, None, :]
+    return dict(seed=seed, nbatch=nbatch, T=T, Vg=Vg, body=base["body"], template_faces=base["template_faces"], rounds=rounds,
+                lbs_pred_garment_v=lbs_pred.reshape(nbatch, T, Vg, 3),
+                inputs=dict(pose_torch=base["batch"]["pose_torch"], smpl_vertices_torch=base["batch"]["smpl_vertices_torch"],
+                            smpl_root_joints_torch=root, garment_torch=garment.astype(F32)))
+
+
+def stage2_loss_checksum(case):
+    items = list(case["rounds"]) + [case["lbs_pred_garment_v"]] + [v for _, v in sorted(case["inputs"].items())]
+    return np.array([float(np.asarray(a, dtype=np.float64).sum()) for a in items])
+
+
 def mgn_displacement_state_dict(vg, seed=0):
     """Seeded weights under the reference's names for the MGN variant's `displacement_encoder` (modules/mesh_encoder.py:518-524:
     Linear 512 -> 1024 -> 2048 -> 3 vg), drawn like torch's default Linear initialisation (uniform +-1/sqrt(in)).  numpy, fp32."""

@@ -748,6 +748,24 @@ int g4d_vertex_normals_f32(int frames, int v, const float *verts, const int *fac
 int g4d_interpenetration_f32(int frames, int vg, int v, const float *garment, const float *body, const float *normals,
                              const int *nn_idx, int idx_stride, float *pen, g4d_stream_t stream);
 
+/* The stage-2 objective of the refinement head for ONE round's prediction (smplx/loss/temporal_loss.py:147-201; csrc/refine_loss.hip):
+ * pred / target (nbatch*t, vg, 3); body / normals (nbatch*t, v, 3); nn_idx int32 with idx_stride ints per garment vertex, the first being the
+ * nearest body vertex (the output of g4d_three_nn_f32: idx_stride 3).  (rowptr, colidx, vals): CSR of the Laplacian L = I - D^-1 A (vg rows,
+ * any row length), rowsum (vg) its row sums (float64 sums of the fp32 entries, rounded); (rowptr_t, colidx_t, vals_t): CSR of L^T, needed
+ * only for the gradient of the Laplacian term.  out (5) = [mean |p-g|^2, mean |p-g|, mean |(L p)_i|, mean relu(-n_b.(p-b)),
+ * temporal != 0 && t > 1 ? mean over (clip, frame < t-1, vertex) of |p_f - p_{f+1}| : 0];  msre_frames (nbatch*t) or NULL: mean |p-g| per frame.
+ * grad (nbatch*t, vg, 3) or NULL (values only): fully written with
+ *   w_l2 d out[0] + w_lap d out[2] + w_pen d out[3] + w_temporal d out[4]  w.r.t. pred;
+ * a zero |(L p)_i| or |p_f - p_{f+1}| contributes zero (the reference's sqrt gives NaN for the latter).  A weight of 0 leaves its value
+ * reported.  No atomics: the sums go through per-workgroup partials in ws (g4d_refine_loss_ws_bytes(nbatch*t, vg, grad != NULL) bytes; with a
+ * gradient it also stages u = L p / |L p|) and are added in an order that depends on the shape alone (the tree is written out in
+ * csrc/refine_loss.hip): two runs give the same bits.  nbatch*t == 0 or vg == 0: out = zeros, nothing else is touched. */
+long long g4d_refine_loss_ws_bytes(int frames, int vg, int with_grad);
+int g4d_refine_loss_f32(int nbatch, int t, int vg, int v, const float *pred, const float *target, const float *body, const float *normals,
+                        const int *nn_idx, int idx_stride, const int *rowptr, const int *colidx, const float *vals, const float *rowsum,
+                        const int *rowptr_t, const int *colidx_t, const float *vals_t, float w_l2, float w_lap, float w_pen, float w_temporal,
+                        int temporal, float *ws, float *out, float *msre_frames, float *grad, g4d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
