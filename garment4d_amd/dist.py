@@ -16,6 +16,8 @@ from typing import List, Tuple
 import torch
 import torch.distributed as dist
 
+from . import _lib
+from . import grad_ops
 from .tuning import current as _T
 
 
@@ -138,7 +140,6 @@ class _TemporalAttentionFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, qkv, T):
-        from . import _lib
         F_, Vg, C = x.shape
         n_clips = F_ // T
         qkv_all = qkv(x).contiguous()
@@ -154,21 +155,20 @@ class _TemporalAttentionFn(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, dout):
-        from . import _lib, refine
         x, weight, qkv_all, att = ctx.saved_tensors
         F_, Vg, C = x.shape
         T = ctx.T
         n_clips, rows = F_ // T, F_ * Vg
-        dout, ldg = refine._grad_window(dout, C)
+        dout, ldg = grad_ops.grad_window(dout, C)
         dqkv = torch.empty_like(qkv_all)
         scratch = torch.empty(_lib.lib().g4d_temporal_attention_grad_scratch_floats(n_clips, Vg, C), dtype=torch.float32, device=x.device)
         _lib.call("g4d_temporal_attention_grad_f32", n_clips, T, Vg, C, qkv_all.data_ptr(), att.data_ptr(), dout.data_ptr(), ldg, 0, scratch.data_ptr(),
                   dqkv.data_ptr(), _lib.stream_ptr())
         dx = dw = None
         if ctx.needs_input_grad[0]:
-            dx = refine._linear_t(dqkv.view(rows, 3 * C), weight).view(F_, Vg, C)
+            dx = grad_ops.linear_t(dqkv.view(rows, 3 * C), weight).view(F_, Vg, C)
         if ctx.needs_input_grad[1]:
-            dw = refine._gemm_tn(rows, C, 3 * C, x, dqkv).t().to(weight.dtype)
+            dw = grad_ops.gemm_tn(rows, C, C, 3 * C, x, dqkv).t().to(weight.dtype)
         return dx, dw, None, None
 
 
@@ -208,7 +208,6 @@ def temporal_attention(last_feat_local: torch.Tensor, frame_ids_local: torch.Ten
     n_clips = F_ // T
     qkv_all = qkv(feats.reshape(n_clips * T, Vg, C))                              # (F, Vg, 3C)
     if feats.is_cuda and T <= 32 and C % 16 == 0:
-        from . import _lib
         qkv_all = qkv_all.contiguous()
         direct = out is not None and not sharded
         res = out if direct else torch.empty((F_, Vg, C), dtype=torch.float32, device=feats.device)

@@ -20,6 +20,7 @@ import os
 import torch
 import torch.nn as nn
 
+from . import _cache
 from . import _lib
 from . import pointnet2_utils as PU
 from .tuning import current as _T
@@ -132,50 +133,28 @@ def _pack_block(block):
     return PackedLayer(w2, scale, shift, relu=act is not None)
 
 
-def _param_key(m):
-    return tuple((p.data_ptr(), _ver(p)) for p in list(m.parameters()) + list(m.buffers()))
+def _params_and_buffers(m):
+    return list(m.parameters()) + list(m.buffers())   # buffers: the BatchNorm running statistics are folded into the packed layers
 
 
 def pack_conv_stack(stack):
     """Pack an nn.Sequential of pytorch_utils.Conv{1,2}d blocks (SharedMLP, FC head).  Dropout is an
     eval-mode no-op.  Cached on the module, keyed by the parameters' version counters."""
-    key = _param_key(stack)
-    cached = getattr(stack, "_g4d_packed", None)
-    if cached is not None and cached[0] == key:
-        return cached[1]
-    with torch.no_grad():
-        layers = [_pack_block(block) for block in stack.children() if not isinstance(block, nn.Dropout)]
-    stack._g4d_packed = (key, layers)
-    return layers
+    return _cache.packed(stack, "packed", _params_and_buffers(stack),
+                         lambda: [_pack_block(block) for block in stack.children() if not isinstance(block, nn.Dropout)])
 
 
 def pack_conv_block(block):
     """One block packed and cached ON THE BLOCK (the drop-in forward of pytorch_utils.Conv1d): PackedLayer."""
-    key = _param_key(block)
-    cached = getattr(block, "_g4d_packed_block", None)
-    if cached is not None and cached[0] == key:
-        return cached[1]
-    with torch.no_grad():
-        layer = _pack_block(block)
-    block._g4d_packed_block = (key, layer)
-    return layer
-
-
-_CACHE_ATTRS = ("_g4d_packed", "_g4d_packed_block", "_g4d_split", "_g4d_pe", "_g4d_table", "_g4d_sa_table", "_g4d_fp_split")
+    return _cache.packed(block, "block", _params_and_buffers(block), lambda: _pack_block(block))
 
 
 def invalidate(module):
-    """Drop every packed-weight cache below `module`.  The caches are keyed on (data_ptr, tensor._version); an in-place
-    update THROUGH `.data` (p.data.copy_, p.data.mul_, EMA swaps, GraphConvolution.reset_parameters) does not bump the
-    version counter, so after such an update call this once -- `load_state_dict` / optimiser steps / plain in-place ops
-    bump the counter and need nothing."""
-    n = 0
-    for m in module.modules():
-        for a in _CACHE_ATTRS:
-            if hasattr(m, a):
-                delattr(m, a)
-                n += 1
-    return n
+    """Drop every packed-weight cache below `module`; returns how many there were.  The caches (_cache.packed: one dict attribute per module)
+    are keyed on (data_ptr, tensor._version); an in-place update THROUGH `.data` (p.data.copy_, p.data.mul_, EMA swaps,
+    GraphConvolution.reset_parameters) does not bump the version counter, so after such an update call this once -- `load_state_dict` /
+    optimiser steps / plain in-place ops bump the counter and need nothing."""
+    return _cache.drop(module)
 
 
 def to_point_major(x):
@@ -683,16 +662,14 @@ def sa_table_fits(layers, C, use_xyz, pool, S, table_rows, grouped_rows):
 def sa_level_table(sa, packed, feats_pm, scales):
     """(table (B*N, sum of the first-layer widths of `scales`), [(column offset, Wx^T (3, Cout1))]): ONE contraction of the level's
     features with the feature columns of every listed scale's first layer -- Wf f_j for every source point j."""
-    key = tuple(id(packed[k][0]) for k in scales)
-    hit = getattr(sa, "_g4d_sa_table", None)
-    if hit is None or hit[0] != key:
-        with torch.no_grad():
-            Wf = torch.cat([packed[k][0].W[:packed[k][0].Cout, 3:packed[k][0].K] for k in scales], 0).contiguous()
-            cat = PackedLayer(Wf, torch.ones(Wf.shape[0], device=Wf.device), torch.zeros(Wf.shape[0], device=Wf.device), relu=False)
-            wx = [packed[k][0].W[:packed[k][0].Cout, :3].t().contiguous() for k in scales]
-        hit = (key, cat, wx, [packed[k][0] for k in scales])   # the first layers are kept alive: their ids are the key
-        sa._g4d_sa_table = hit
-    _, cat, wx, _ = hit
+    firsts = [packed[k][0] for k in scales]
+
+    def build():
+        Wf = torch.cat([L.W[:L.Cout, 3:L.K] for L in firsts], 0).contiguous()
+        cat = PackedLayer(Wf, torch.ones(Wf.shape[0], device=Wf.device), torch.zeros(Wf.shape[0], device=Wf.device), relu=False)
+        return cat, [L.W[:L.Cout, :3].t().contiguous() for L in firsts], firsts   # the first layers are kept alive: their ids are the key
+
+    cat, wx, _ = _cache.packed(sa, "sa_table", (), build, extra=tuple(id(L) for L in firsts))
     B, N, C = feats_pm.shape
     table = linear(feats_pm.view(B * N, C), cat)
     offs, c0 = [], 0
@@ -918,6 +895,19 @@ def three_nn_multi(pairs):
 # (FP_WIDE_TABLE -> tuning.Tuning.fp_wide_table) wide FP levels with skip features: known-feature columns pre-contracted, interpolation added in the GEMM's epilogue
 
 
+def _fp_split(fp, L0, C2, C1):
+    """The first FP layer split by input columns, W [interp(f) ; s] = interp(Wa f) + Wb s: (La, the C2 known-feature columns as a bare
+    contraction; Lb, the C1 skip columns with the layer's affine and ReLU)."""
+    def build():
+        W0 = L0.W[:L0.Cout, :L0.K]
+        ones, zeros = torch.ones(L0.Cout, device=W0.device), torch.zeros(L0.Cout, device=W0.device)
+        La = PackedLayer(W0[:, :C2].contiguous(), ones, zeros, relu=False)
+        Lb = PackedLayer(W0[:, C2:C2 + C1].contiguous(), L0.scale[:L0.Cout], L0.shift[:L0.Cout], relu=bool(L0.relu))
+        return La, Lb, L0   # L0 kept alive: its id is the key
+
+    return _cache.packed(fp, "fp_split", (), build, extra=id(L0))[:2]
+
+
 def fp_table_layer(fp, C1, C2, head):
     """The raw first layer (PackedLayer, scale 1 / shift 0 / no ReLU) of an FP level that fp_forward would run on a pre-contracted table
     (no skip features), or None: a caller that produces this level's known features with another chain launch can append it there as one
@@ -1014,18 +1004,7 @@ def fp_forward(fp, unknown, known, unknow_feats_pm, known_feats_pm, head=None, u
             and m < n and chain_fits(layers, 0, 1, 2)):
         # Skip features: W [interp(f) ; s] = interp(Wa f) + Wb s -- the known-feature columns of the first layer are contracted over the
         # m KNOWN rows (table), the first layer's accumulators start from the interpolated table and the matrix pipe adds the skip columns.
-        key = id(layers[0])
-        hit = getattr(fp, "_g4d_fp_split", None)
-        if hit is None or hit[0] != key:
-            L0 = layers[0]
-            with torch.no_grad():
-                W0 = L0.W[:L0.Cout, :L0.K]
-                ones, zeros = torch.ones(L0.Cout, device=W0.device), torch.zeros(L0.Cout, device=W0.device)
-                La = PackedLayer(W0[:, :C2].contiguous(), ones, zeros, relu=False)
-                Lb = PackedLayer(W0[:, C2:C2 + C1].contiguous(), L0.scale[:L0.Cout], L0.shift[:L0.Cout], relu=bool(L0.relu))
-            hit = (key, La, Lb, L0)   # L0 kept alive: its id is the key
-            fp._g4d_fp_split = hit
-        _, La, Lb, _ = hit
+        La, Lb = _fp_split(fp, layers[0], C2, C1)
         table = linear(known_feats_pm.view(B * m, C2), La)
         rest = [Lb] + layers[1:]
         tapl, tap_t, fin = -1, None, out.view(B * n, -1)
@@ -1077,17 +1056,7 @@ def fp_forward(fp, unknown, known, unknow_feats_pm, known_feats_pm, head=None, u
         # (g4d_linear_interp_add_f32); no interpolated + concatenated matrix is written.  Round 2 measured this at 8 clouds (one more launch on
         # 2048 rows: 45.3 -> 47.1 us alone) and dropped it; at the executor's 240 clouds per call the level is flop-bound and it wins
         # (471 -> ~200 us).  Taken at EVERY batch size: a cloud's result must not depend on how many clouds share the call.
-        hit = getattr(fp, "_g4d_fp_split", None)
-        if hit is None or hit[0] != id(layers[0]):
-            L0 = layers[0]
-            with torch.no_grad():
-                W0 = L0.W[:L0.Cout, :L0.K]
-                ones, zeros = torch.ones(L0.Cout, device=W0.device), torch.zeros(L0.Cout, device=W0.device)
-                La = PackedLayer(W0[:, :C2].contiguous(), ones, zeros, relu=False)
-                Lb = PackedLayer(W0[:, C2:C2 + C1].contiguous(), L0.scale[:L0.Cout], L0.shift[:L0.Cout], relu=bool(L0.relu))
-            hit = (id(L0), La, Lb, L0)
-            fp._g4d_fp_split = hit
-        _, La, Lb, _ = hit
+        La, Lb = _fp_split(fp, layers[0], C2, C1)
         table = linear(known_feats_pm.view(B * m, C2), La)
         h = out.view(B * n, -1) if len(layers) == 1 else torch.empty((B * n, Lb.Cout), dtype=torch.float32, device=unknown.device)
         _lib.call("g4d_linear_interp_add_f32", B * n, n, m, C1, Lb.Kpad, Lb.Cout, _chk(unknow_feats_pm).data_ptr(), C1, Lb.W.data_ptr(), table.data_ptr(),

@@ -11,6 +11,7 @@ kernel gathers rows; the per-frame weights are blended with the clip's neighbour
 import numpy as np
 import torch
 
+from . import _cache
 from . import _lib
 from . import lbs as L
 from .gcn import _to_csr, normalize
@@ -34,27 +35,22 @@ def smoothing_operator(adj_old, coeff, iters, device):
     """The `iters` Jacobi steps  W <- W + coeff * ((D^-1 A - I) . W)  are ONE linear map along the vertex axis:
     M = ((1 - coeff) I + coeff D^-1 A)^iters, a dense row-stochastic (Vg,Vg) matrix (100 hops cover the mesh).  Built once
     per mesh by repeated squaring in fp64 on the device, kept in fp32."""
-    key = (id(adj_old), float(coeff), int(iters), str(device))
-    hit = _operator_cache.get(key)
-    if hit is not None and hit[0] is adj_old:
-        return hit[1]
-    import scipy.sparse as sp
-    n = adj_old.shape[0]
-    step = (sp.eye(n) * (1.0 - coeff) + normalize(adj_old) * coeff).tocoo()
-    base = torch.sparse_coo_tensor(torch.from_numpy(np.vstack((step.row, step.col)).astype(np.int64)), torch.from_numpy(step.data.astype(np.float64)),
-                                   (n, n)).to(device).to_dense()
-    M, e = None, int(iters)
-    while e:                                   # square-and-multiply, fp64 library GEMMs
-        if e & 1:
-            M = base if M is None else M @ base
-        e >>= 1
-        if e:
-            base = base @ base
-    M = (torch.eye(n, dtype=torch.float64, device=device) if M is None else M).float().contiguous()
-    if len(_operator_cache) > 4:
-        _operator_cache.clear()
-    _operator_cache[key] = (adj_old, M)
-    return M
+    def build():
+        import scipy.sparse as sp
+        n = adj_old.shape[0]
+        step = (sp.eye(n) * (1.0 - coeff) + normalize(adj_old) * coeff).tocoo()
+        base = torch.sparse_coo_tensor(torch.from_numpy(np.vstack((step.row, step.col)).astype(np.int64)), torch.from_numpy(step.data.astype(np.float64)),
+                                       (n, n)).to(device).to_dense()
+        M, e = None, int(iters)
+        while e:                                   # square-and-multiply, fp64 library GEMMs
+            if e & 1:
+                M = base if M is None else M @ base
+            e >>= 1
+            if e:
+                base = base @ base
+        return (torch.eye(n, dtype=torch.float64, device=device) if M is None else M).float().contiguous()
+
+    return _cache.by_identity(_operator_cache, 4, (adj_old,), (float(coeff), int(iters), str(device)), build)
 
 
 _SMOOTH_OPERATOR_MAX_VG = 8192   # dense operator up to 256 MB; larger meshes run the sparse steps
@@ -66,18 +62,13 @@ _smooth_csr_cache = {}
 def _smoothing_csr(adj_old, device):
     """(rowptr, colidx, vals, n, longest row) of D^-1 A - I on `device`, built once per adjacency object (scipy work + three H2D
     copies: neither belongs in a forward that may be running under hipGraph capture)."""
-    key = (id(adj_old), str(device))
-    hit = _smooth_csr_cache.get(key)
-    if hit is not None and hit[0] is adj_old:
-        return hit[1]
-    import scipy.sparse as sp
-    adj = sp.csr_matrix(normalize(adj_old) - sp.eye(adj_old.shape[0]))
-    max_row = int(np.diff(adj.indptr).max()) if adj.shape[0] else 0
-    val = _to_csr(adj, device) + (max_row,)
-    if len(_smooth_csr_cache) > 8:
-        _smooth_csr_cache.clear()
-    _smooth_csr_cache[key] = (adj_old, val, adj)   # `adj` pinned: _to_csr caches by object identity
-    return val
+    def build():
+        import scipy.sparse as sp
+        adj = sp.csr_matrix(normalize(adj_old) - sp.eye(adj_old.shape[0]))
+        max_row = int(np.diff(adj.indptr).max()) if adj.shape[0] else 0
+        return _to_csr(adj, device) + (max_row,), adj   # `adj` pinned: _to_csr caches by object identity
+
+    return _cache.by_identity(_smooth_csr_cache, 8, (adj_old,), str(device), build)[0]
 
 
 def smooth_weights(nn_W, adj_old, coeff=0.1, iters=100, method=None):

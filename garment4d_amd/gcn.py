@@ -31,7 +31,9 @@ import numpy as np
 import torch
 from torch.nn.parameter import Parameter
 
+from . import _cache
 from . import _lib
+from . import grad_ops
 from .tuning import current as _T
 from .fused import PackedLayer, linear
 
@@ -101,16 +103,7 @@ def _csr_tensors(m, device):
 
 def _to_csr(adj, device):
     """torch sparse (COO/CSR) or scipy sparse -> (rowptr, colidx, vals) int32/float32 on `device`, cached per object."""
-    key = (id(adj), str(device))
-    hit = _csr_cache.get(key)
-    if hit is not None and hit[0] is adj:
-        return hit[1]
-    m = _scipy_csr(adj)
-    if len(_csr_cache) > 32:
-        _csr_cache.clear()
-    csr = _csr_tensors(m, device)
-    _csr_cache[key] = (adj, csr)
-    return csr
+    return _cache.by_identity(_csr_cache, 32, (adj,), str(device), lambda: _csr_tensors(_scipy_csr(adj), device))
 
 
 _csr_t_cache = {}
@@ -119,18 +112,13 @@ _csr_t_cache = {}
 def _to_csr_t(adj, device):
     """The CSR of adj^T -- (rowptr, colidx, vals, n) like _to_csr, cached per adjacency object: row u lists the v with adj[v, u] != 0 in
     ASCENDING v, which is the summation order of dS = adj^T G in g4d_spmm_rows_grad_f32 (a defined order: the gradient is reproducible)."""
-    key = (id(adj), str(device))
-    hit = _csr_t_cache.get(key)
-    if hit is not None and hit[0] is adj:
-        return hit[1]
-    mt = _scipy_csr(adj).T.tocsr()
-    mt.sum_duplicates()
-    mt.sort_indices()
-    if len(_csr_t_cache) > 32:
-        _csr_t_cache.clear()
-    csr = _csr_tensors(mt, device)
-    _csr_t_cache[key] = (adj, csr)
-    return csr
+    def build():
+        mt = _scipy_csr(adj).T.tocsr()
+        mt.sum_duplicates()
+        mt.sort_indices()
+        return _csr_tensors(mt, device)
+
+    return _cache.by_identity(_csr_t_cache, 32, (adj,), str(device), build)
 
 
 _meta_cache = {}
@@ -181,36 +169,29 @@ class GraphConvolution(torch.nn.Module):
             self.bias.data.uniform_(-stdv, stdv)
 
     def _packed(self):
-        key = (self.weight.data_ptr(), _lib.ver(self.weight), None if self.bias is None else (self.bias.data_ptr(), _lib.ver(self.bias)))
-        hit = getattr(self, "_g4d_packed", None)
-        if hit is None or hit[0] != key:
-            with torch.no_grad():
-                dev = self.weight.device
-                zero = torch.zeros(self.out_features, device=dev)
-                bias = self.bias.detach().float().contiguous() if self.bias is not None else None
-                wt = self.weight.detach().float().t().contiguous()
-                one = torch.ones(self.out_features, device=dev)
-                L = (PackedLayer(wt, one, zero, relu=False),                          # support = X W
-                     PackedLayer(wt, one, bias if bias is not None else zero, relu=False),  # ismlp: X W + b
-                     bias)
-            hit = (key, L)
-            self._g4d_packed = hit
-        return hit[1]
+        def build():
+            dev = self.weight.device
+            zero = torch.zeros(self.out_features, device=dev)
+            bias = self.bias.detach().float().contiguous() if self.bias is not None else None
+            wt = self.weight.detach().float().t().contiguous()
+            one = torch.ones(self.out_features, device=dev)
+            return (PackedLayer(wt, one, zero, relu=False),                          # support = X W
+                    PackedLayer(wt, one, bias if bias is not None else zero, relu=False),  # ismlp: X W + b
+                    bias)
+
+        return _cache.packed(self, "packed", [self.weight] if self.bias is None else [self.weight, self.bias], build)
 
     def _packed_support_padded(self, width):
         """The support contraction for an input whose rows carry `width` >= in_features columns, the extra ones ZERO (the caller pads a ragged
         feature width -- 323, 195 -- to a multiple of 4 so that the rows are 16-byte aligned and the tiled GEMM takes the launch): the weight
         gets zero rows for them, every partial sum keeps its value and its k order -- the same bits as _packed()[0] on the unpadded rows."""
-        key = (self.weight.data_ptr(), _lib.ver(self.weight), int(width))
-        hit = getattr(self, "_g4d_packed_pad", None)
-        if hit is None or hit[0] != key:
-            with torch.no_grad():
-                dev = self.weight.device
-                wt = torch.zeros((self.out_features, int(width)), dtype=torch.float32, device=dev)
-                wt[:, :self.in_features] = self.weight.detach().float().t()
-                hit = (key, PackedLayer(wt, torch.ones(self.out_features, device=dev), torch.zeros(self.out_features, device=dev), relu=False))
-            self._g4d_packed_pad = hit
-        return hit[1]
+        def build():
+            dev = self.weight.device
+            wt = torch.zeros((self.out_features, int(width)), dtype=torch.float32, device=dev)
+            wt[:, :self.in_features] = self.weight.detach().float().t()
+            return PackedLayer(wt, torch.ones(self.out_features, device=dev), torch.zeros(self.out_features, device=dev), relu=False)
+
+        return _cache.packed(self, "support_padded", [self.weight], build, extra=int(width))
 
     def forward(self, input, adj, ismlp=False, relu=False):
         """input (B,N,Fin) or (N,Fin); adj sparse (N,N).  ismlp=True skips the aggregation (layers.py:43,51).
@@ -255,15 +236,12 @@ class GraphConvolution(torch.nn.Module):
 
     def _packed_transposed(self):
         """W itself as the "transposed weight" of a contraction over Cout: dX = dS . W^T through g4d_linear_f32 (K = Cout, Cout = Fin)."""
-        key = (self.weight.data_ptr(), _lib.ver(self.weight))
-        hit = getattr(self, "_g4d_packed_t", None)
-        if hit is None or hit[0] != key:
-            with torch.no_grad():
-                dev = self.weight.device
-                hit = (key, PackedLayer(self.weight.detach().float().contiguous(), torch.ones(self.in_features, device=dev),
-                                        torch.zeros(self.in_features, device=dev), relu=False))
-            self._g4d_packed_t = hit
-        return hit[1]
+        def build():
+            dev = self.weight.device
+            return PackedLayer(self.weight.detach().float().contiguous(), torch.ones(self.in_features, device=dev),
+                               torch.zeros(self.in_features, device=dev), relu=False)
+
+        return _cache.packed(self, "transposed", [self.weight], build)
 
     def __repr__(self):
         return f"{self.__class__.__name__} ({self.in_features} -> {self.out_features})"
@@ -296,9 +274,7 @@ class _GCNLayerFn(torch.autograd.Function):
         yp = y.data_ptr() if y is not None else 0
         dx = dw = db = None
         if need_b:   # column sums of G
-            db = torch.empty(cout, dtype=torch.float32, device=dev)
-            ws = torch.empty(max(int(_lib.lib().g4d_col_sum_rows_ws_bytes(rows, cout)) // 4, 1), dtype=torch.float32, device=dev)
-            _lib.call("g4d_col_sum_rows_f32", rows, cout, dy.data_ptr(), yp, ws.data_ptr(), db.data_ptr(), stream)
+            db = grad_ops.col_sum(rows, cout, dy, y)
         if need_x or need_w:
             if ctx.ismlp:    # no aggregation: dS = G
                 ds = dy if y is None else torch.where(y > 0, dy, torch.zeros((), dtype=torch.float32, device=dev))
@@ -309,9 +285,7 @@ class _GCNLayerFn(torch.autograd.Function):
                 _lib.call("g4d_spmm_rows_grad_f32", B, N, cout, dy.data_ptr(), yp, rowptr_t.data_ptr(), colidx_t.data_ptr(), vals_t.data_ptr(),
                           ds.data_ptr(), stream)
             if need_w:       # dW = X^T dS over the first `fin` columns of the (possibly padded) rows
-                dw = torch.empty((fin, cout), dtype=torch.float32, device=dev)
-                ws = torch.empty(max(int(_lib.lib().g4d_gemm_tn_ws_bytes(rows, fin, cout)) // 4, 1), dtype=torch.float32, device=dev)
-                _lib.call("g4d_gemm_tn_f32", rows, fin, ldx, cout, x.data_ptr(), ds.data_ptr(), ws.data_ptr(), dw.data_ptr(), stream)
+                dw = grad_ops.gemm_tn(rows, fin, ldx, cout, x, ds)
                 if dw.dtype != weight.dtype:
                     dw = dw.to(weight.dtype)
             if need_x:       # dX = dS W^T; the zero columns of a padded input get zero gradient

@@ -1,0 +1,45 @@
+"""Launch helpers the backward passes share (gcn._GCNLayerFn, refine._FeatureTableFn / _PosEncodeFn, dist._TemporalAttentionFn): each wraps
+one kernel with its full argument set and sizes its workspace, so that kernel has one Python call site."""
+import torch
+
+from . import _lib
+from . import fused
+
+
+def grad_window(g, width):
+    """A cotangent (F, V, width) as (tensor, leading dimension): the column window of a wider row-major buffer (what the backward of
+    torch.cat hands over) is read in place through its row stride; anything else is made contiguous."""
+    if g.dtype != torch.float32:
+        g = g.float()
+    F_, V, _ = g.shape
+    if g.stride(2) == 1 and g.stride(1) >= width and g.stride(0) == V * g.stride(1):
+        return g, g.stride(1)
+    return g.contiguous(), width
+
+
+def col_sum(rows, c, g, mask=None):
+    """Column sums (c,) of the (rows, c) matrix g, of the entries where mask > 0 when a mask (the output of a fused ReLU) is given:
+    g4d_col_sum_rows_f32."""
+    out = torch.empty(c, dtype=torch.float32, device=g.device)
+    ws = torch.empty(max(int(_lib.lib().g4d_col_sum_rows_ws_bytes(rows, c)) // 4, 1), dtype=torch.float32, device=g.device)
+    _lib.call("g4d_col_sum_rows_f32", rows, c, g.data_ptr(), 0 if mask is None else mask.data_ptr(), ws.data_ptr(), out.data_ptr(),
+              _lib.stream_ptr())
+    return out
+
+
+def gemm_tn(rows, fin, ldx, cout, x, ds):
+    """X^T dS (fin, cout) over `rows` rows, X being the first fin columns of rows ldx >= fin apart: g4d_gemm_tn_f32, slice partials added
+    in a fixed order."""
+    dw = torch.empty((fin, cout), dtype=torch.float32, device=x.device)
+    ws = torch.empty(max(int(_lib.lib().g4d_gemm_tn_ws_bytes(rows, fin, cout)) // 4, 1), dtype=torch.float32, device=x.device)
+    _lib.call("g4d_gemm_tn_f32", rows, fin, ldx, cout, x.data_ptr(), ds.data_ptr(), ws.data_ptr(), dw.data_ptr(), _lib.stream_ptr())
+    return dw
+
+
+def linear_t(ds2d, weight):
+    """dS . W for a Linear weight W (Cout, Cin): g4d_linear_f32 with W^T as the packed (Cin x Cout-deep) layer."""
+    cin = weight.shape[1]
+    with torch.no_grad():
+        L = fused.PackedLayer(weight.detach().float().t().contiguous(), torch.ones(cin, device=weight.device),
+                              torch.zeros(cin, device=weight.device), relu=False)
+    return fused.linear(ds2d, L)

@@ -10,6 +10,7 @@ that remain available in the reference's own lbs.py).
 """
 import torch
 
+from . import _cache
 from . import _lib
 from .tuning import current as _T
 
@@ -24,13 +25,8 @@ def _f32(t, name):
 
 
 def _parents_i32(parents, device):
-    key = (id(parents), str(device))
-    hit = _parents_cache.get(key)
-    if hit is not None and hit[0] is parents:
-        return hit[1]
-    p = torch.as_tensor(parents).to(device=device, dtype=torch.int32).contiguous()
-    _parents_cache[key] = (parents, p)
-    return p
+    return _cache.by_identity(_parents_cache, float("inf"), (parents,), str(device),
+                              lambda: torch.as_tensor(parents).to(device=device, dtype=torch.int32).contiguous())
 
 
 import os
@@ -52,22 +48,17 @@ def _model_constants(v_template, shapedirs, posedirs, J_regressor):
     """[shapedirs^T ; posedirs] ((NB+PF), V*3), J_regressor v_template (J,3), J_regressor shapedirs (J,3,NB): constants of a body
     model, computed once (the two regressor products in float64) and cached on the tensors' identities."""
     src = (v_template, shapedirs, posedirs, J_regressor)
-    key = tuple((id(t), _lib.ver(t)) for t in src)
-    hit = _const_cache.get(key)
-    if hit is not None and not all(a is b for a, b in zip(hit[3], src)):
-        hit = None                       # an id recycled by a new tensor: the entry keeps its sources alive, so this cannot happen while cached
-    if hit is None:
+
+    def build():
         V, _, NB = shapedirs.shape
         with torch.no_grad():
             blend_dirs = torch.cat([shapedirs.reshape(V * 3, NB).t(), posedirs], 0).contiguous()
             Jr = J_regressor.double()
             Jt = (Jr @ v_template.double()).float().contiguous()
             Js = torch.einsum("jv,vrk->jrk", Jr, shapedirs.double()).float().contiguous()
-        if len(_const_cache) > 8:
-            _const_cache.clear()
-        hit = (blend_dirs, Jt, Js, src)     # holding `src` pins the ids the key is made of
-        _const_cache[key] = hit
-    return hit[:3]
+        return blend_dirs, Jt, Js
+
+    return _cache.by_identity(_const_cache, 8, src, tuple(_lib.ver(t) for t in src), build)
 
 
 def _require(cond, msg):

@@ -7,6 +7,7 @@ layers (ties -> lowest index, like knn_points here), not from a K=1 top-K search
 import numpy as np
 import torch
 
+from . import _cache
 from . import _lib
 from . import fused
 from . import mesh_utils
@@ -64,31 +65,26 @@ def laplacian_csr(lap_adj, device):
     sums of the fp32 entries) and the CSR of L^T (L's pattern on a symmetric mesh, values -1/deg of the OTHER vertex), all on `device`.
     Recovered from the matrix itself -- whatever the caller built it from -- once per object (cached by identity, like
     garment_lbs._smoothing_csr): scipy work and seven host-to-device copies, which do not belong inside a hipGraph capture."""
-    key = (id(lap_adj), str(device))
-    hit = _lap_cache.get(key)
-    if hit is not None and hit[0] is lap_adj:
-        return hit[1]
-    assert not torch.cuda.is_current_stream_capturing(), "laplacian_csr: build the operator before the capture (call the loss once eagerly)"
-    import scipy.sparse as sp
-    if torch.is_tensor(lap_adj):
-        c = lap_adj.detach().coalesce() if lap_adj.is_sparse else lap_adj.detach().to_sparse().coalesce()
-        ij = c.indices().cpu().numpy()
-        L = sp.csr_matrix((c.values().float().cpu().numpy(), (ij[0], ij[1])), shape=tuple(c.shape))
-    else:
-        L = sp.csr_matrix(lap_adj).astype(np.float32)
-    assert L.shape[0] == L.shape[1], "the Laplacian is square"
-    L.sum_duplicates()
-    L.sort_indices()
-    Lt = sp.csr_matrix(L.T)
-    Lt.sort_indices()
-    rowsum = np.asarray(L.astype(np.float64).sum(1)).reshape(-1).astype(np.float32)
-    dev = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a).astype(dt)).to(device)
-    val = (dev(L.indptr, np.int32), dev(L.indices, np.int32), dev(L.data, np.float32), dev(rowsum, np.float32),
-           dev(Lt.indptr, np.int32), dev(Lt.indices, np.int32), dev(Lt.data, np.float32))
-    if len(_lap_cache) > 8:
-        _lap_cache.clear()
-    _lap_cache[key] = (lap_adj, val)
-    return val
+    def build():
+        assert not torch.cuda.is_current_stream_capturing(), "laplacian_csr: build the operator before the capture (call the loss once eagerly)"
+        import scipy.sparse as sp
+        if torch.is_tensor(lap_adj):
+            c = lap_adj.detach().coalesce() if lap_adj.is_sparse else lap_adj.detach().to_sparse().coalesce()
+            ij = c.indices().cpu().numpy()
+            L = sp.csr_matrix((c.values().float().cpu().numpy(), (ij[0], ij[1])), shape=tuple(c.shape))
+        else:
+            L = sp.csr_matrix(lap_adj).astype(np.float32)
+        assert L.shape[0] == L.shape[1], "the Laplacian is square"
+        L.sum_duplicates()
+        L.sort_indices()
+        Lt = sp.csr_matrix(L.T)
+        Lt.sort_indices()
+        rowsum = np.asarray(L.astype(np.float64).sum(1)).reshape(-1).astype(np.float32)
+        dev = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a).astype(dt)).to(device)
+        return (dev(L.indptr, np.int32), dev(L.indices, np.int32), dev(L.data, np.float32), dev(rowsum, np.float32),
+                dev(Lt.indptr, np.int32), dev(Lt.indices, np.int32), dev(Lt.data, np.float32))
+
+    return _cache.by_identity(_lap_cache, 8, (lap_adj,), str(device), build)
 
 
 def _lambdas(loss_cfg):

@@ -23,7 +23,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib
+from . import _cache
 from . import dist as gdist
 from . import fused
 from . import gcn
@@ -46,12 +46,8 @@ def _any_training(module):
 
 def _pack_plain_stack(seq):
     """nn.Sequential of nn.Conv1d(k=1) [nn.BatchNorm1d] [nn.ReLU] -> packed layers (eval-mode BN folded), cached."""
-    key = tuple((p.data_ptr(), _lib.ver(p)) for p in list(seq.parameters()) + list(seq.buffers()))
-    hit = getattr(seq, "_g4d_packed", None)
-    if hit is not None and hit[0] == key:
-        return hit[1]
-    mods, layers, i = list(seq.children()), [], 0
-    with torch.no_grad():
+    def build():
+        mods, layers, i = list(seq.children()), [], 0
         while i < len(mods):
             conv = mods[i]
             assert isinstance(conv, nn.Conv1d) and conv.kernel_size == (1,), "plain stack: 1x1 Conv1d expected"
@@ -63,8 +59,9 @@ def _pack_plain_stack(seq):
             i += int(relu)
             scale, shift = fused._fold(conv, bn)
             layers.append(fused.PackedLayer(conv.weight.detach().float().squeeze(-1), scale, shift, relu=relu))
-    seq._g4d_packed = (key, layers)
-    return layers
+        return layers
+
+    return _cache.packed(seq, "packed", list(seq.parameters()) + list(seq.buffers()), build)
 
 
 class PCAGarmentEncoderSeg(nn.Module):
@@ -104,18 +101,21 @@ class PCAGarmentEncoderSeg(nn.Module):
         self.garment_f_3 = mesh_utils.quads2tris(self.remesh_cylinder_f).astype(np.int32)
         self.garment_v_num = self.remesh_cylinder_v.shape[0]
 
-    def PCA_inverse_transform(self, coeff):
-        assert coeff.shape[1] == self.pca_dim
-        dev = coeff.device
+    def _pca_layer(self, dev):
+        """coeff (nbatch, pca_dim) . components (pca_dim, 3 Vg), then + mean, * scale, as ONE packed layer with the affine folded into its
+        epilogue -- (x W^T + mean) * scale = x W^T * scale + mean * scale; rebuilt when a PCA tensor moves or is written in place."""
         self.PCA_comp, self.PCA_mean = self.PCA_comp.to(dev), self.PCA_mean.to(dev)
         self.PCA_expl, self.PCA_scale = self.PCA_expl.to(dev), self.PCA_scale.to(dev)
-        # coeff (nbatch, pca_dim) . components (pca_dim, 3 Vg), then + mean, * scale: ONE launch of the MFMA layer kernel with the
-        # affine folded into its epilogue -- (x W^T + mean) * scale = x W^T * scale + mean * scale
-        key = (self.PCA_comp.data_ptr(), self.PCA_mean.data_ptr(), self.PCA_scale.data_ptr(), str(dev))
-        if getattr(self, "_pca_layer", (None,))[0] != key:
+
+        def build():
             sc = self.PCA_scale.float().reshape(-1).expand(self.PCA_comp.shape[1]).contiguous()   # scalar or per-coordinate scale
-            self._pca_layer = (key, fused.PackedLayer(self.PCA_comp.float().t().contiguous(), sc, self.PCA_mean.float() * sc, relu=False))
-        return fused.linear(coeff.float().contiguous(), self._pca_layer[1]).reshape(coeff.shape[0], -1, 3)
+            return fused.PackedLayer(self.PCA_comp.float().t().contiguous(), sc, self.PCA_mean.float() * sc, relu=False)
+
+        return _cache.packed(self, "pca", [self.PCA_comp, self.PCA_mean, self.PCA_scale], build, extra=str(dev))
+
+    def PCA_inverse_transform(self, coeff):
+        assert coeff.shape[1] == self.pca_dim
+        return fused.linear(coeff.float().contiguous(), self._pca_layer(coeff.device)).reshape(coeff.shape[0], -1, 3)   # one MFMA layer launch
 
     def calc_segmentation_results(self, x, sem_logits, n, nbatch, T, feature_pm):
         """mesh_encoder.py:109-125 on point-major tensors; returns (garment_v (F,n,3), garment_f (F,n,C) point-major)."""
@@ -314,14 +314,9 @@ class PCALBSGarmentUseSegEncoderSegMGN(nn.Module):
     def _displacement_layers(self):
         """The three Linear layers as packed HIP layers (bias as the shift), rebuilt when a parameter changes."""
         mods = [m for m in self.displacement_encoder if isinstance(m, nn.Linear)]
-        key = tuple((p.data_ptr(), _lib.ver(p), str(p.device)) for p in self.displacement_encoder.parameters())
-        hit = getattr(self, "_g4d_disp", None)
-        if hit is None or hit[0] != key:
-            with torch.no_grad():
-                layers = [fused.PackedLayer(m.weight.detach().float(), torch.ones(m.out_features, device=m.weight.device), m.bias.detach().float(),
-                                            relu=i < len(mods) - 1) for i, m in enumerate(mods)]
-            hit = self._g4d_disp = (key, layers)
-        return hit[1]
+        return _cache.packed(self, "disp", self.displacement_encoder.parameters(), lambda: [
+            fused.PackedLayer(m.weight.detach().float(), torch.ones(m.out_features, device=m.weight.device), m.bias.detach().float(),
+                              relu=i < len(mods) - 1) for i, m in enumerate(mods)], extra=str(mods[0].weight.device))
 
     def displacements(self, garment_summary):
         """(F, 512) garment summary -> (F, Vg, 3) displacements: the MLP on the HIP linear kernels, * 0.05, NaN -> 0 (:597-601)."""

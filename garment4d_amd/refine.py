@@ -14,9 +14,11 @@ against oracle/refine_oracle.py."""
 import torch
 import torch.nn as nn
 
+from . import _cache
 from . import _lib
 from . import dist as gdist
 from . import fused
+from . import grad_ops
 from . import tuning as _tuning
 from .tuning import current as _T
 from .gcn import GraphConvolution, gcn_stack_forward
@@ -27,20 +29,17 @@ from .gcn import GraphConvolution, gcn_stack_forward
 
 def _pack_linear_mlp(seq):
     """nn.Sequential(Linear, ReLU, Linear) -> packed layers (cached on the module)."""
-    key = tuple((p.data_ptr(), _lib.ver(p)) for p in seq.parameters())
-    hit = getattr(seq, "_g4d_packed", None)
-    if hit is not None and hit[0] == key:
-        return hit[1]
-    layers, mods = [], list(seq.children())
-    with torch.no_grad():
+    def build():
+        layers, mods = [], list(seq.children())
         for i, m in enumerate(mods):
             if isinstance(m, nn.Linear):
                 relu = i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU)
                 dev = m.weight.device
                 bias = m.bias.detach().float() if m.bias is not None else torch.zeros(m.out_features, device=dev)
                 layers.append(fused.PackedLayer(m.weight.detach().float(), torch.ones(m.out_features, device=dev), bias, relu=relu))
-    seq._g4d_packed = (key, layers)
-    return layers
+        return layers
+
+    return _cache.packed(seq, "packed", seq.parameters(), build)
 
 
 def _split_first_linear(seq):
@@ -50,21 +49,18 @@ def _split_first_linear(seq):
     (query, sample) pair (Vg * S rows), and the grouped row shrinks from 3 + C (up to 387) to 3 + H = 35 columns
     [x_j - q ; G_j] against the weight [Wx | I].  The coordinate difference is still formed first, in fp32, as the
     reference does; only the summation order of the feature dot product changes."""
-    key = tuple((p.data_ptr(), _lib.ver(p)) for p in seq.parameters())
-    hit = getattr(seq, "_g4d_split", None)
-    if hit is not None and hit[0] == key:
-        return hit[1], hit[2]
-    lin0, lin2 = seq[0], seq[2]
-    H, dev = lin0.out_features, lin0.weight.device
-    with torch.no_grad():
+    def build():
+        lin0, lin2 = seq[0], seq[2]
+        H, dev = lin0.out_features, lin0.weight.device
         W = lin0.weight.detach().float()
         ones, zeros = torch.ones(H, device=dev), torch.zeros(H, device=dev)
         table = fused.PackedLayer(W[:, 3:].contiguous(), ones, lin0.bias.detach().float(), relu=False)
         first = fused.PackedLayer(torch.cat([W[:, :3], torch.eye(H, device=dev)], 1), ones, zeros, relu=True)
         second = fused.PackedLayer(lin2.weight.detach().float(), torch.ones(lin2.out_features, device=dev), lin2.bias.detach().float(),
                                    relu=False)
-    seq._g4d_split = (key, table, [first, second])
-    return table, [first, second]
+        return table, [first, second]
+
+    return _cache.packed(seq, "split", seq.parameters(), build)
 
 
 def _pe_stack(layers, idx, nsample, xyz, new_xyz, feats_pm, out, col0):
@@ -89,15 +85,12 @@ def _pe_kernel_weights(seq, n_in):
             and seq[0].out_features == 32 and seq[2].in_features == 32 and seq[2].out_features == 32 and seq[2].bias is not None
             and seq[0].bias is not None):
         return None
-    key = (tuple((p.data_ptr(), _lib.ver(p)) for p in seq.parameters()), n_in)
-    hit = getattr(seq, "_g4d_pe", None)
-    if hit is None or hit[0] != key:
-        with torch.no_grad():
-            W1 = seq[0].weight.detach().float()[:, :n_in].contiguous()
-            second = fused.PackedLayer(seq[2].weight.detach().float(), torch.ones(32, device=W1.device), seq[2].bias.detach().float(), relu=False)
-            hit = (key, (W1, seq[0].bias.detach().float().contiguous(), second.Wf, seq[2].bias.detach().float().contiguous()))
-        seq._g4d_pe = hit
-    return hit[1]
+    def build():
+        W1 = seq[0].weight.detach().float()[:, :n_in].contiguous()
+        second = fused.PackedLayer(seq[2].weight.detach().float(), torch.ones(32, device=W1.device), seq[2].bias.detach().float(), relu=False)
+        return W1, seq[0].bias.detach().float().contiguous(), second.Wf, seq[2].bias.detach().float().contiguous()
+
+    return _cache.packed(seq, "pe", seq.parameters(), build, extra=n_in)
 
 
 def positional_encoding(mlp, radius, nsample, xyz, new_xyz, feats_pm, out, col0, idx=None, table=None, _kernel_only=False):
@@ -135,41 +128,6 @@ def feature_table(mlp, feats_pm):
 
 
 # ---------------------------------------------------------------------------------------------------------------- training route (opt-in)
-def _grad_window(g, width):
-    """A cotangent (F, V, width) as (tensor, leading dimension): the column window of a wider row-major buffer (what the backward of
-    torch.cat hands over) is read in place through its row stride; anything else is made contiguous."""
-    if g.dtype != torch.float32:
-        g = g.float()
-    F_, V, _ = g.shape
-    if g.stride(2) == 1 and g.stride(1) >= width and g.stride(0) == V * g.stride(1):
-        return g, g.stride(1)
-    return g.contiguous(), width
-
-
-def _col_sum(rows, c, x):
-    out = torch.empty(c, dtype=torch.float32, device=x.device)
-    ws = torch.empty(max(int(_lib.lib().g4d_col_sum_rows_ws_bytes(rows, c)) // 4, 1), dtype=torch.float32, device=x.device)
-    _lib.call("g4d_col_sum_rows_f32", rows, c, x.data_ptr(), 0, ws.data_ptr(), out.data_ptr(), _lib.stream_ptr())
-    return out
-
-
-def _gemm_tn(rows, fin, cout, x, ds):
-    """X^T dS (fin, cout) over `rows` rows: g4d_gemm_tn_f32, slice partials added in a fixed order."""
-    dw = torch.empty((fin, cout), dtype=torch.float32, device=x.device)
-    ws = torch.empty(max(int(_lib.lib().g4d_gemm_tn_ws_bytes(rows, fin, cout)) // 4, 1), dtype=torch.float32, device=x.device)
-    _lib.call("g4d_gemm_tn_f32", rows, fin, fin, cout, x.data_ptr(), ds.data_ptr(), ws.data_ptr(), dw.data_ptr(), _lib.stream_ptr())
-    return dw
-
-
-def _linear_t(ds2d, weight):
-    """dS . W for a Linear weight W (Cout, Cin): g4d_linear_f32 with W^T as the packed (Cin x Cout-deep) layer."""
-    cin = weight.shape[1]
-    with torch.no_grad():
-        L = fused.PackedLayer(weight.detach().float().t().contiguous(), torch.ones(cin, device=weight.device),
-                              torch.zeros(cin, device=weight.device), relu=False)
-    return fused.linear(ds2d, L)
-
-
 class _FeatureTableFn(torch.autograd.Function):
     """G = Wf f + b1 per source point (feature_table: the same launch and bits); backward over kernels that exist: dWf = dG^T f
     (g4d_gemm_tn_f32), db1 = column sums of dG (g4d_col_sum_rows_f32), df = dG Wf (g4d_linear_f32)."""
@@ -188,11 +146,11 @@ class _FeatureTableFn(torch.autograd.Function):
         dG = dG.contiguous().float()
         df = dWf = db = None
         if ctx.needs_input_grad[0]:
-            df = _linear_t(dG.view(rows, H), Wf).view(F_, N, C)
+            df = grad_ops.linear_t(dG.view(rows, H), Wf).view(F_, N, C)
         if ctx.needs_input_grad[1]:
-            dWf = _gemm_tn(rows, C, H, feats, dG).t().to(Wf.dtype)
+            dWf = grad_ops.gemm_tn(rows, C, C, H, feats, dG).t().to(Wf.dtype)
         if ctx.needs_input_grad[2]:
-            db = _col_sum(rows, H, dG)
+            db = grad_ops.col_sum(rows, H, dG)
         return df, dWf, db, None
 
 
@@ -219,7 +177,7 @@ class _PosEncodeFn(torch.autograd.Function):
         F_, N, Vg, S, n_extra = ctx.dims
         dev = xyz.device
         need = ctx.needs_input_grad
-        dout, ldg = _grad_window(dout, 32)
+        dout, ldg = grad_ops.grad_window(dout, 32)
         W1c, W2c = W1.detach().float().contiguous(), W2.detach().float().contiguous()
         f32 = dict(dtype=torch.float32, device=dev)
         d_new = torch.empty((F_, Vg, 3), **f32) if need[0] else None
@@ -289,17 +247,24 @@ class GarmentRefinementHead(nn.Module):
         self.lbs_graph_regress2 = gcn(self.graph_start_feature_dim + self.hidden_dim)
         self.lbs_graph_regress3 = gcn(self.graph_start_feature_dim + self.hidden_dim)
 
+    def _stages(self):
+        """The sub-modules in the order the rounds use them: body encoders, garment encoders (per level), qkv Linears (rounds 1, 2) and
+        regressors (per round)."""
+        return ([self.body_positional_encoding0, self.body_positional_encoding1, self.body_positional_encoding2],
+                [self.garment_positional_encoding0, self.garment_positional_encoding1, self.garment_positional_encoding2],
+                [self.temporal_qkv_1, self.temporal_qkv_2],
+                [self.lbs_graph_regress1, self.lbs_graph_regress2, self.lbs_graph_regress3])
+
+    def _round_width(self, it):
+        """(width, wpad) of round `it`'s GCN input: 195 / 323 columns, and the row padded to 16 bytes (zero columns) so that the tiled GEMM
+        takes the regressor's first contraction."""
+        width = self.graph_start_feature_dim + (self.hidden_dim if it > 0 else 0)
+        return width, (width + 3) // 4 * 4
+
     def _qkv(self, lin):
-        key = (lin.weight.data_ptr(), _lib.ver(lin.weight))
-        hit = getattr(lin, "_g4d_packed", None)
-        if hit is None or hit[0] != key:
-            dev = lin.weight.device
-            with torch.no_grad():
-                L = fused.PackedLayer(lin.weight.detach().float(), torch.ones(lin.out_features, device=dev),
-                                      torch.zeros(lin.out_features, device=dev), relu=False)
-            hit = (key, L)
-            lin._g4d_packed = hit
-        L = hit[1]
+        dev = lin.weight.device
+        L = _cache.packed(lin, "packed", [lin.weight], lambda: fused.PackedLayer(
+            lin.weight.detach().float(), torch.ones(lin.out_features, device=dev), torch.zeros(lin.out_features, device=dev), relu=False))
         return lambda x: fused.linear(x.reshape(-1, x.shape[-1]).contiguous(), L).view(*x.shape[:-1], -1)
 
     def forward(self, cur_garment_v, body_v, body_vn, garment_v_list, garment_f_list, adj, nbatch, T, group=None, frame_ids=None,
@@ -312,10 +277,7 @@ class GarmentRefinementHead(nn.Module):
             return self._forward_autograd(cur_garment_v, body_v, body_vn, garment_v_list, garment_f_list, adj, nbatch, T, group)
         assert not torch.is_grad_enabled(), ("GarmentRefinementHead is inference-only: call under torch.no_grad() (or opt in to the backward "
                                              "kernels: tuning.Tuning.refine_autograd / G4D_REFINE_AUTOGRAD=1)")
-        body_pe = [self.body_positional_encoding0, self.body_positional_encoding1, self.body_positional_encoding2]
-        garm_pe = [self.garment_positional_encoding0, self.garment_positional_encoding1, self.garment_positional_encoding2]
-        qkvs = [self.temporal_qkv_1, self.temporal_qkv_2]
-        regress = [self.lbs_graph_regress1, self.lbs_graph_regress2, self.lbs_graph_regress3]
+        body_pe, garm_pe, qkvs, regress = self._stages()
         F_, Vg, _ = cur_garment_v.shape
         dev = cur_garment_v.device
         if frame_ids is None:
@@ -328,8 +290,7 @@ class GarmentRefinementHead(nn.Module):
         tables = [feature_table(garm_pe[i], garment_f_list[i].contiguous()) if garment_f_list[i].shape[2] > self.feat_num else None
                   for i in range(3)]
         for it in range(self.iteration):
-            width = self.graph_start_feature_dim + (self.hidden_dim if it > 0 else 0)
-            wpad = (width + 3) // 4 * 4    # 195 / 323 columns: rows padded to 16 bytes (zero columns) so that the tiled GEMM takes the regressor's first contraction
+            width, wpad = self._round_width(it)
             feat = torch.empty((F_, Vg, wpad), dtype=torch.float32, device=dev)
             if wpad > width:
                 feat[..., width:] = 0
@@ -368,10 +329,7 @@ class GarmentRefinementHead(nn.Module):
         require grad; body_v / body_vn are constants; the ball-query indices are constants of the graph (the reference's QueryAndGroup)."""
         if group is not None and group is not False:
             raise NotImplementedError("GarmentRefinementHead: frame-sharded runs (group=...) are inference-only; train with whole clips per rank")
-        body_pe = [self.body_positional_encoding0, self.body_positional_encoding1, self.body_positional_encoding2]
-        garm_pe = [self.garment_positional_encoding0, self.garment_positional_encoding1, self.garment_positional_encoding2]
-        qkvs = [self.temporal_qkv_1, self.temporal_qkv_2]
-        regress = [self.lbs_graph_regress1, self.lbs_graph_regress2, self.lbs_graph_regress3]
+        body_pe, garm_pe, qkvs, regress = self._stages()
         F_, Vg, _ = cur_garment_v.shape
         dev = cur_garment_v.device
         n_frames = nbatch * T
@@ -391,8 +349,7 @@ class GarmentRefinementHead(nn.Module):
                 tables.append(None)
         with _tuning.use(_T().replace(gcn_autograd=True)):
             for it in range(self.iteration):
-                width = self.graph_start_feature_dim + (self.hidden_dim if it > 0 else 0)
-                wpad = (width + 3) // 4 * 4
+                width, wpad = self._round_width(it)
                 with torch.no_grad():
                     body_idx = fused.ball_query_msg(self.body_radius_list, self.body_sample_num_list, body_v, cur.detach(), coherent=True)
                     garm_idx = [fused.ball_query_msg([self.garment_radius_list[i]], [self.garment_sample_num_list[i]], gv[i].detach(), cur.detach())[0]

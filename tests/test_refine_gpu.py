@@ -167,6 +167,64 @@ def test_attention_only_mixes_frames_of_a_clip():
     assert not torch.equal(a[-1][T:], b[-1][T:])
 
 
+def _fresh_copy(head):
+    fresh = GarmentRefinementHead().cuda().eval()
+    fresh.load_state_dict(head.state_dict())
+    return fresh
+
+
+def test_invalidate_after_a_data_update_serves_the_new_weights():
+    """A head that has packed every cache, gets its parameters scaled THROUGH .data (no version bump) and is invalidated must compute what a
+    fresh head holding the updated weights computes: the same kernels, operands and launch order, so the same bits in every round.  (The 195- and
+    323-wide first regressor layers run on the zero-padded pack, which invalidate() once missed.)"""
+    from garment4d_amd import fused
+    nbatch, T = 2, 3
+    head, _, *inputs = _case(nbatch, T, seed=3)
+    _run(head, *inputs, nbatch, T)
+    for p in head.parameters():
+        p.data.mul_(0.75)
+    assert fused.invalidate(head) > 0
+    got = _run(head, *inputs, nbatch, T)
+    fresh = _fresh_copy(head)
+    want, again = _run(fresh, *inputs, nbatch, T), _run(fresh, *inputs, nbatch, T)
+    assert len(got) == len(want) == 3
+    for r in range(3):
+        assert torch.equal(want[r], again[r]), f"round {r}: the head is not bit-reproducible from run to run"
+        assert torch.isfinite(got[r]).all() and torch.equal(got[r], want[r]), f"round {r}: max |diff| {float((got[r] - want[r]).abs().max()):.3g}"
+
+
+def test_invalidate_after_a_data_update_on_the_training_route():
+    """The same on the training route (tuning.Tuning.refine_autograd): the forward bits of every round and the gradient of each regressor's
+    first-layer weight, which reaches it through the transposed-weight packs (dX = dS W^T) of the layers behind it."""
+    from garment4d_amd import fused, tuning
+    nbatch, T = 2, 3
+    head, _, cur, body_v, body_vn, gv, gf, adj = _case(nbatch, T, seed=3)
+    adj_t = G.sparse_mx_to_torch_sparse_tensor(adj).cuda()
+    args = (dev(cur), dev(body_v), dev(body_vn), [dev(x) for x in gv], [dev(x) for x in gf], adj_t, nbatch, T)
+    cots = [dev(np.random.default_rng(40 + r).standard_normal(cur.shape).astype(np.float32)) for r in range(3)]
+
+    def run(h):
+        h.zero_grad(set_to_none=True)
+        with tuning.use(tuning.current().replace(refine_autograd=True)):
+            outs = h(*args)
+        torch.autograd.backward(outs, cots)
+        firsts = [reg[0].weight.grad.clone() for reg in (h.lbs_graph_regress1, h.lbs_graph_regress2, h.lbs_graph_regress3)]
+        return [o.detach() for o in outs], firsts
+
+    run(head)
+    for p in head.parameters():
+        p.data.mul_(0.75)
+    assert fused.invalidate(head) > 0
+    got_out, got_grad = run(head)
+    fresh = _fresh_copy(head)
+    (want_out, want_grad), (again_out, again_grad) = run(fresh), run(fresh)
+    for r in range(3):
+        assert torch.equal(want_out[r], again_out[r]) and torch.equal(want_grad[r], again_grad[r]), f"round {r}: not bit-reproducible from run to run"
+        assert torch.equal(got_out[r], want_out[r]), f"round {r}: max |diff| {float((got_out[r] - want_out[r]).abs().max()):.3g}"
+        assert torch.isfinite(got_grad[r]).all() and got_grad[r].abs().max() > 0
+        assert torch.equal(got_grad[r], want_grad[r]), f"regressor {r + 1}: max |diff| {float((got_grad[r] - want_grad[r]).abs().max()):.3g}"
+
+
 @pytest.mark.parametrize("nclips,T,Vg,C", [(2, 30, 300, 128), (1, 3, 17, 16), (3, 32, 64, 48), (1, 1, 5, 32)])
 def test_temporal_attention_kernels(nclips, T, Vg, C):
     """csrc/attention.hip against float64 torch (mesh_encoder.py:467-476), written at a column offset."""
