@@ -6,13 +6,15 @@ symmetrised garment-mesh adjacency, :299-303) are passed explicitly because this
 Differences that do not change results: ONE K-nearest search serves the K, min(64,K) and K=1 queries of :321-324 (the
 sorted K=256 list contains the others as prefixes); the (V,J) weight table is never `.repeat`-ed K times -- the blend
 kernel gathers rows; the per-frame weights are blended with the clip's neighbour list without materialising the
-(B*T, Vg, K, J) tensor of :381-382.  Forward only.
+(B*T, Vg, K, J) tensor of :381-382.  Forward only -- except lbs_garment_MGN (the MGN variant's nearest-vertex skinning), which is
+differentiable in the garment (csrc/mgn_skin_grad.hip).
 """
 import numpy as np
 import torch
 
 from . import _cache
 from . import _lib
+from . import grad_ops
 from . import lbs as L
 from .gcn import _to_csr, normalize
 from .knn import KNN, knn_points
@@ -176,6 +178,45 @@ def _inv_template_pose_mats(F_, device):
     return L.batch_rodrigues(inv_pose.reshape(-1, 3)).reshape(1, 24, 3, 3).expand(F_, 24, 3, 3).contiguous()
 
 
+class _MGNSkinFn(torch.autograd.Function):
+    """g4d_mgn_skin_f32 as an autograd node, differentiable in the garment alone.  forward = the inference launch (same bits); saved: the nearest
+    index and the three tables both blends read; backward = ONE launch of g4d_mgn_skin_grad_f32 (csrc/mgn_skin_grad.hip), which recomputes the
+    blends at the saved index.  Outputs: (posed, stage 1, index, squared distance); index and distance are not differentiable."""
+
+    @staticmethod
+    def forward(ctx, garment, root, body, W, inv_A, A, clips, T):
+        idx, dists, stage1, posed = _mgn_skin(clips, T, garment, root, body, W, inv_A, A)
+        ctx.clips, ctx.T = clips, T
+        ctx.save_for_backward(idx, W, inv_A, A)
+        ctx.mark_non_differentiable(idx, dists)
+        return posed, stage1, idx, dists
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_posed, d_stage1, _d_idx, _d_dists):
+        idx, W, inv_A, A = ctx.saved_tensors
+        if d_posed is None:                        # only stage 1 was used downstream
+            d_posed = torch.zeros((idx.shape[0], idx.shape[1], 3), dtype=torch.float32, device=idx.device)
+        d_posed = d_posed.float().contiguous()
+        if d_stage1 is not None:
+            d_stage1 = d_stage1.float().contiguous()
+        return (grad_ops.mgn_skin_grad(ctx.clips, ctx.T, idx, W, inv_A, A, d_posed, d_stage1),) + (None,) * 7
+
+
+def _mgn_skin(clips, T, garment, root, body, W, inv_A, A):
+    """The one call site of g4d_mgn_skin_f32 -> (idx (F,Vg,1) int32, dists (F,Vg,1), stage1 (F,Vg,3), posed (F,Vg,3))."""
+    F_, Vg = garment.shape[0], garment.shape[1]
+    V, J = body.shape[1], W.shape[2]
+    dev = garment.device
+    idx = torch.empty((F_, Vg, 1), dtype=torch.int32, device=dev)
+    dists = torch.empty((F_, Vg, 1), dtype=torch.float32, device=dev)
+    stage1 = torch.empty((F_, Vg, 3), dtype=torch.float32, device=dev)
+    posed = torch.empty((F_, Vg, 3), dtype=torch.float32, device=dev)
+    _lib.call("g4d_mgn_skin_f32", clips, T, Vg, V, J, garment.data_ptr(), root.data_ptr(), body.data_ptr(), W.data_ptr(), inv_A.data_ptr(),
+              A.data_ptr(), idx.data_ptr(), dists.data_ptr(), stage1.data_ptr(), posed.data_ptr(), _lib.stream_ptr())
+    return idx, dists, stage1, posed
+
+
 def lbs_garment_MGN(pred_template_garment_v, Tpose_vertices, Tpose_root_joints, zeropose_vertices, parents, gt_pose, T_J_regressor,
                     T_lbs_weights, K=1):
     """`PCALBSGarmentUseSegEncoderSegMGN.lbs_garment_MGN` (modules/mesh_encoder.py:529-585).  pred_template_garment_v (B,T,Vg,3);
@@ -184,33 +225,43 @@ def lbs_garment_MGN(pred_template_garment_v, Tpose_vertices, Tpose_root_joints, 
     un-posed by the inverse template pose (B,T,Vg,3)).
     The joints and the two sets of joint transforms come from the lbs helpers (inv_A: per-frame regressor on the clip's T-pose, :548-550;
     A: per-frame regressor on the zero-pose vertices, :562-564); the K = 1 search and both blends at the nearest vertex are ONE launch
-    (g4d_mgn_skin_f32): the (B*T, V, 4, 4) blends of :553 / :568 never exist."""
+    (g4d_mgn_skin_f32): the (B*T, V, 4, 4) blends of :553 / :568 never exist.
+    Differentiable in its FIRST argument (posed and stage 1; the nearest index is a constant of the graph, as knn_points(...).idx is in the
+    reference): under grad with a grad-requiring garment the same launch runs as an autograd node whose backward is g4d_mgn_skin_grad_f32.
+    Any other input that requires grad raises NotImplementedError; the nearest-vertex KNN is never differentiable."""
     assert pred_template_garment_v.dim() == 4 and pred_template_garment_v.shape[-1] == 3
     assert gt_pose.dim() == 3 and gt_pose.shape[2] == 72
     assert K == 1
+    train = torch.is_grad_enabled() and pred_template_garment_v.requires_grad
+    if torch.is_grad_enabled():
+        for name, t in (("Tpose_vertices", Tpose_vertices), ("Tpose_root_joints", Tpose_root_joints), ("zeropose_vertices", zeropose_vertices),
+                        ("gt_pose", gt_pose), ("T_J_regressor", T_J_regressor), ("T_lbs_weights", T_lbs_weights)):
+            if t.requires_grad:
+                raise NotImplementedError(f"lbs_garment_MGN: {name} requires grad -- only pred_template_garment_v is differentiated (the body, the "
+                                          "pose and the skinning tables are constants of the graph)")
     B, T = gt_pose.shape[0], gt_pose.shape[1]
     F_ = B * T
     dev = gt_pose.device
     Vg = pred_template_garment_v.shape[2]
     J = T_J_regressor.shape[2]
-    body = L._f32(Tpose_vertices, "Tpose_vertices").reshape(B, -1, 3)
-    V = body.shape[1]
     garment = L._f32(pred_template_garment_v, "pred_template_garment_v").reshape(F_, Vg, 3)
-    root = L._f32(Tpose_root_joints, "Tpose_root_joints").reshape(B, 3)
-    Jreg = L._f32(T_J_regressor, "T_J_regressor").reshape(F_, J, V)
-    W = L._f32(T_lbs_weights, "T_lbs_weights").reshape(F_, V, J)
-    if not (tuple(pred_template_garment_v.shape[:2]) == (B, T) and tuple(T_lbs_weights.shape) == (B, T, V, J)
-            and tuple(T_J_regressor.shape) == (B, T, J, V) and zeropose_vertices.numel() == F_ * V * 3):
-        raise RuntimeError("lbs_garment_MGN: inputs disagree on (B, T, Vg, V, J)")
-    gt_pose_mat = L.batch_rodrigues(gt_pose.reshape(-1, 3).contiguous()).reshape(F_, 24, 3, 3)
-    body_f = body.reshape(B, 1, V, 3).expand(B, T, V, 3).reshape(F_, V, 3)       # new_Tpose_vertices (:540)
-    _, inv_A = L.batch_rigid_transform(_inv_template_pose_mats(F_, dev), L.vertices2jointsB(Jreg, body_f), parents)
-    Jz = L.vertices2jointsB(Jreg, zeropose_vertices.reshape(F_, V, 3))
-    _, A = L.batch_rigid_transform(gt_pose_mat, Jz, parents)
-    idx = torch.empty((F_, Vg, 1), dtype=torch.int32, device=dev)
-    dists = torch.empty((F_, Vg, 1), dtype=torch.float32, device=dev)
-    stage1 = torch.empty((F_, Vg, 3), dtype=torch.float32, device=dev)
-    posed = torch.empty((F_, Vg, 3), dtype=torch.float32, device=dev)
-    _lib.call("g4d_mgn_skin_f32", B, T, Vg, V, J, garment.data_ptr(), root.data_ptr(), body.data_ptr(), W.data_ptr(), inv_A.data_ptr(),
-              A.data_ptr(), idx.data_ptr(), dists.data_ptr(), stage1.data_ptr(), posed.data_ptr(), _lib.stream_ptr())
+    with torch.no_grad():
+        body = L._f32(Tpose_vertices, "Tpose_vertices").reshape(B, -1, 3)
+        V = body.shape[1]
+        root = L._f32(Tpose_root_joints, "Tpose_root_joints").reshape(B, 3)
+        Jreg = L._f32(T_J_regressor, "T_J_regressor").reshape(F_, J, V)
+        W = L._f32(T_lbs_weights, "T_lbs_weights").reshape(F_, V, J)
+        if not (tuple(pred_template_garment_v.shape[:2]) == (B, T) and tuple(T_lbs_weights.shape) == (B, T, V, J)
+                and tuple(T_J_regressor.shape) == (B, T, J, V) and zeropose_vertices.numel() == F_ * V * 3):
+            raise RuntimeError("lbs_garment_MGN: inputs disagree on (B, T, Vg, V, J)")
+        gt_pose_mat = L.batch_rodrigues(gt_pose.reshape(-1, 3).contiguous()).reshape(F_, 24, 3, 3)
+        body_f = body.reshape(B, 1, V, 3).expand(B, T, V, 3).reshape(F_, V, 3)       # new_Tpose_vertices (:540)
+        _, inv_A = L.batch_rigid_transform(_inv_template_pose_mats(F_, dev), L.vertices2jointsB(Jreg, body_f), parents)
+        Jz = L.vertices2jointsB(Jreg, zeropose_vertices.reshape(F_, V, 3))
+        _, A = L.batch_rigid_transform(gt_pose_mat, Jz, parents)
+    if train:
+        posed, stage1, idx, dists = _MGNSkinFn.apply(garment, root, body, W, inv_A, A, B, T)
+    else:
+        with torch.no_grad():
+            idx, dists, stage1, posed = _mgn_skin(B, T, garment, root, body, W, inv_A, A)
     return posed.reshape(B, T, Vg, 3), KNN(dists=dists, idx=idx.long(), knn=None), stage1.reshape(B, T, Vg, 3)

@@ -1,4 +1,5 @@
-"""Launch helpers the backward passes share (gcn._GCNLayerFn, refine._FeatureTableFn / _PosEncodeFn, dist._TemporalAttentionFn): each wraps
+"""Launch helpers the backward passes share (gcn._GCNLayerFn, refine._FeatureTableFn / _PosEncodeFn, dist._TemporalAttentionFn,
+garment_lbs._MGNSkinFn, mesh_encoder._LinearFn): each wraps
 one kernel with its full argument set and sizes its workspace, so that kernel has one Python call site."""
 import torch
 
@@ -34,6 +35,17 @@ def gemm_tn(rows, fin, ldx, cout, x, ds):
     ws = torch.empty(max(int(_lib.lib().g4d_gemm_tn_ws_bytes(rows, fin, cout)) // 4, 1), dtype=torch.float32, device=x.device)
     _lib.call("g4d_gemm_tn_f32", rows, fin, ldx, cout, x.data_ptr(), ds.data_ptr(), ws.data_ptr(), dw.data_ptr(), _lib.stream_ptr())
     return dw
+
+
+def mgn_skin_grad(clips, frames_per_clip, idx, W, inv_A, A, d_posed, d_stage1=None):
+    """d garment (F, Vg, 3) of lbs_garment_MGN for the fixed nearest index idx (F, Vg) int32 -- M_inv^T (M^T d_posed + d_stage1) with the
+    forward's blends recomputed: g4d_mgn_skin_grad_f32.  d_stage1 None: zero."""
+    F_, V, J = W.shape
+    Vg = idx.shape[1]
+    out = torch.empty((F_, Vg, 3), dtype=torch.float32, device=W.device)
+    _lib.call("g4d_mgn_skin_grad_f32", clips, frames_per_clip, Vg, V, J, idx.data_ptr(), W.data_ptr(), inv_A.data_ptr(), A.data_ptr(),
+              d_posed.data_ptr(), 0 if d_stage1 is None else d_stage1.data_ptr(), out.data_ptr(), _lib.stream_ptr())
+    return out
 
 
 def linear_t(ds2d, weight):

@@ -11,7 +11,9 @@ so a reference checkpoint's `state_dict` loads by key:
 
 Inference only -- except PCALBSGarmentUseSegEncoderSeg.forward under grad with tuning.Tuning.refine_autograd
 on: the reference's second training stage (encoder, normals and skinning under no_grad, the refinement head under grad; the objective is
-losses.temporal_loss_PCA_LBS).  What the constructor needs from disk in the reference (the PCA basis pickle
+losses.temporal_loss_PCA_LBS), and PCALBSGarmentUseSegEncoderSegMGN.forward under grad with tuning.Tuning.mgn_autograd on: the reference's MGN training
+(train_temporal.py --MGN 1; encoder under no_grad, the displacement MLP and the nearest-vertex skinning under grad, the same objective).
+What the constructor needs from disk in the reference (the PCA basis pickle
 and the garment template OBJ, both part of the CLOTH3D-derived data set that is not available here) can be given either
 through the reference's cfg (`cfg.GARMENT.PCACOMPONENTSFILE`, `cfg.GARMENT.TEMPLATE`) or as arrays.  Frames may be
 sharded over ranks: pass `group` / `frame_ids`; the exchanges are the clip max of the garment summary (all-reduce MAX of
@@ -27,6 +29,7 @@ from . import _cache
 from . import dist as gdist
 from . import fused
 from . import gcn
+from . import grad_ops
 from . import mesh_utils
 from . import tuning
 from .encoder import Pointnet2MSGSEG
@@ -287,6 +290,49 @@ class PCALBSGarmentUseSegEncoderSeg(GarmentRefinementHead):
 
 
 
+class _LinearFn(torch.autograd.Function):
+    """One nn.Linear (+ fused ReLU) of the MGN displacement MLP as an autograd node.  forward = fused.linear on the cached packed layer (the
+    inference route's launch and bits); saved: X, W, and Y only when the ReLU is fused (its mask is Y > 0).  backward, on existing kernels
+    (grad_ops): with G = dY (masked by Y > 0),  db = column sums of G,  dW (Cout, Cin) = G^T X  as g4d_gemm_tn_f32 with G in the "X" role -- the
+    (Cout, Cin) matrix is written directly, never transposed --,  dX = G W  through the transposed pack of `module` (_cache.packed, keyed on the
+    weight's version: rebuilt after an optimizer step, not before)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, module, layer):
+        y = fused.linear(x, layer)
+        ctx.module, ctx.relu = module, bool(layer.relu)
+        ctx.save_for_backward(x, weight, y if layer.relu else None)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, weight, y = ctx.saved_tensors
+        rows, cin = x.shape
+        cout = weight.shape[0]
+        dy = dy.float().contiguous()
+        dx = dw = db = None
+        if ctx.needs_input_grad[2]:
+            db = grad_ops.col_sum(rows, cout, dy, y).to(weight.dtype)
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            g = dy if y is None else torch.where(y > 0, dy, torch.zeros((), dtype=torch.float32, device=dy.device))
+            if ctx.needs_input_grad[1]:
+                dw = grad_ops.gemm_tn(rows, cout, cout, cin, g, x).to(weight.dtype)
+            if ctx.needs_input_grad[0]:
+                dx = fused.linear(g, _packed_transposed(ctx.module))
+        return dx, dw, db, None, None
+
+
+def _packed_transposed(linear):
+    """W^T of an nn.Linear as the packed (Cin x Cout-deep) layer of dX = G W, cached on the module under the weight's version.  A NaN weight
+    enters as 0: the displacement path zeroes the output of a NaN row and with it the row's cotangent (G is exactly 0 there), so its term of G W
+    is 0 -- on the matrix cores 0 * NaN would instead turn every gradient in front of the layer into NaN."""
+    w = linear.weight
+    return _cache.packed(linear, "packed_t", [w], lambda: fused.PackedLayer(
+        torch.nan_to_num(w.detach().float().t(), nan=0.0, posinf=float("inf"), neginf=float("-inf")).contiguous(), torch.ones(w.shape[1], device=w.device),
+        torch.zeros(w.shape[1], device=w.device), relu=False), extra=str(w.device))
+
+
 class PCALBSGarmentUseSegEncoderSegMGN(nn.Module):
     """The MGN baseline (modules/mesh_encoder.py:489-614; train_temporal.py builds it for `--MGN 1`): the PCA garment encoder, a per-frame
     displacement MLP on the garment summary, and nearest-body-vertex skinning (`lbs_garment_MGN`, one HIP launch for the search and both
@@ -321,6 +367,14 @@ class PCALBSGarmentUseSegEncoderSegMGN(nn.Module):
     def displacements(self, garment_summary):
         """(F, 512) garment summary -> (F, Vg, 3) displacements: the MLP on the HIP linear kernels, * 0.05, NaN -> 0 (:597-601)."""
         h = garment_summary.reshape(-1, 512).float().contiguous()
+        if torch.is_grad_enabled() and tuning.current().mgn_autograd:
+            # the training route: the same launches, each Linear an autograd node (_LinearFn); the scale and the NaN guard out of place, so the
+            # cotangent is exactly 0 where the forward wrote 0 for a NaN (torch's index_put in the reference, :599-601)
+            mods = [m for m in self.displacement_encoder if isinstance(m, nn.Linear)]
+            for m, layer in zip(mods, self._displacement_layers()):
+                h = _LinearFn.apply(h, m.weight, m.bias, m, layer)
+            d = h.reshape(h.shape[0], -1, 3) * 0.05
+            return d.masked_fill(torch.isnan(d), 0.0)
         for layer in self._displacement_layers():
             h = fused.linear(h, layer)
         d = h.reshape(h.shape[0], -1, 3) * 0.05
@@ -336,11 +390,22 @@ class PCALBSGarmentUseSegEncoderSegMGN(nn.Module):
     def forward(self, x, body_model, batch, *, precision="fp32"):
         """x (nbatch, T, N, 3); body_model needs `.parents`; batch holds the reference's keys (`Tpose_smpl_vertices_torch`,
         `Tpose_smpl_root_joints_torch`, `zeropose_smpl_vertices_torch`, `pose_torch`, `T_J_regressor`, `T_lbs_weights`) with the same
-        leading (nbatch, T) as x.  precision as in PCALBSGarmentUseSegEncoderSeg.forward (the encoder's MLP operands only)."""
-        assert not torch.is_grad_enabled() and not _any_training(self), "inference only: model.eval() (every submodule) under torch.no_grad()"
+        leading (nbatch, T) as x.  precision as in PCALBSGarmentUseSegEncoderSeg.forward (the encoder's MLP operands only).
+        Training (opt-in, tuning.Tuning.mgn_autograd; the reference's train_temporal.py --MGN 1): under grad the encoder -- entirely in eval()
+        -- runs under torch.no_grad(), as in the reference (:591-592), and only `displacements` and `lbs_garment_MGN` build a graph: the
+        objective (losses.temporal_loss_PCA_LBS) then fills .grad of the six displacement_encoder parameters and of nothing else.  Same
+        launches, same output keys, same bits as the inference route; fp32 only."""
+        train = torch.is_grad_enabled() and tuning.current().mgn_autograd
+        if train:
+            assert not _any_training(self.PCA_garment_encoder), "inference only: model.eval() (every submodule) under torch.no_grad()"
+            if precision != "fp32":
+                raise NotImplementedError(f"PCALBSGarmentUseSegEncoderSegMGN.forward under grad: precision='{precision}' -- the backward kernels are "
+                                          "fp32 only")
+        else:
+            assert not torch.is_grad_enabled() and not _any_training(self), "inference only: model.eval() (every submodule) under torch.no_grad()"
         nbatch, T = x.size(0), x.size(1)
         dev = x.device
-        with fused.precision(precision):
+        with fused.precision(precision), torch.no_grad():
             out = self.PCA_garment_encoder(x, body_model, group=False)    # whole clips on this rank: no exchange
         out["lap_adj"] = self._lap_adj_on(dev)
         regressed = out["tpose_garment"].reshape(nbatch, 1, -1, 3)
@@ -358,7 +423,10 @@ class PCALBSGarmentUseSegEncoderSegMGN(nn.Module):
         (F_local,72), `T_J_regressor` (F_local,J,V), `T_lbs_weights` (F_local,V,J)) and per-CLIP tensors for all clips
         (`Tpose_smpl_vertices_torch` (nbatch,V,3), `Tpose_smpl_root_joints_torch` (nbatch,3)).  The one exchange is the encoder's
         all-reduce MAX of the (nbatch, 512) garment summary; everything after it is per frame.  Same output keys as `forward`, for the
-        local frames (`lbs_pred_garment_v` / `lbs_stage1_pred_garment_v` (F_local,Vg,3), `lbs_nn` with (F_local,Vg,1))."""
+        local frames (`lbs_pred_garment_v` / `lbs_stage1_pred_garment_v` (F_local,Vg,3), `lbs_nn` with (F_local,Vg,1)).  Inference only."""
+        if torch.is_grad_enabled() and tuning.current().mgn_autograd:
+            raise NotImplementedError("PCALBSGarmentUseSegEncoderSegMGN.forward_frames under grad: frame-sharded training is not implemented "
+                                      "(forward() trains whole clips per rank)")
         assert not torch.is_grad_enabled() and not _any_training(self), "inference only: model.eval() (every submodule) under torch.no_grad()"
         dev = x.device
         ids = [int(i) for i in frame_ids]

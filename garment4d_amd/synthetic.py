@@ -290,6 +290,29 @@ def mgn_golden_case(seed=90, nbatch=2, T=3):
                 tpose_garment=tpose_garment, garment_summary=garment_summary, pred_template=pred_template)
 
 
+def mgn_grad_targets(case, posed, seed=190, body_scale=(1.5, 1.0, 1.5)):
+    """The loss inputs of tests/golden/mgn_grad.npz (written by tests/golden/make_golden_mgn_grad.py, which runs the reference's MGN forward,
+    its `temporal_loss_PCA_LBS` and autograd on mgn_golden_case plus these): random root joints, a `garment_torch` within about a centimetre of
+    `posed` (nbatch, T, Vg, 3) -- the reference's own forward output for the case, tests/golden/mgn.npz `fwd_posed` -- relative to the root, as
+    the loss adds it back, and the loss's body `smpl_vertices_torch` = the scene's, widened by body_scale about each frame's centroid: against
+    the scene's own body 81.9 % of the posed garment penetrates, against the widened one 53.6 % (the generator asserts 20-80 %), with no
+    vertex closer than 1e-4 to the tangent plane of its nearest body vertex.  mgn_grad_checksum() guards against generator drift."""
+    nbatch, T, Vg = case["nbatch"], case["T"], case["Vg"]
+    rng = np.random.default_rng(seed)
+    root = rng.normal(0.0, 0.05, (nbatch, T, 3)).astype(F32)
+    garment = (np.asarray(posed, F32).reshape(nbatch, T, Vg, 3) + rng.normal(0.0, 0.01, (nbatch, T, Vg, 3))).astype(F32) - root[:, :, None, :]
+    body = case["batch"]["smpl_vertices_torch"]
+    centre = body.mean(2, keepdims=True)
+    body = ((body - centre) * np.asarray(body_scale, F32) + centre).astype(F32)
+    return dict(garment_torch=garment.astype(F32), smpl_root_joints_torch=root, smpl_vertices_torch=body)
+
+
+def mgn_grad_checksum(case, targets):
+    items = [case["tpose_garment"], case["garment_summary"]] + [v for _, v in sorted(case["batch"].items())] + [v for _, v in sorted(targets.items())]
+    items += [v for _, v in sorted(mgn_displacement_state_dict(case["Vg"], seed=case["seed"] + 100).items())]
+    return np.array([float(np.asarray(a, dtype=np.float64).sum()) for a in items])
+
+
 def encoder_state_dict(shapes, seed=0):
     """Seeded weights for a PointNet++ encoder / PCAGarmentEncoderSeg given its state-dict {key: shape} (keys drawn in sorted order, so
     the reference's model and this package's give the same values).  Multi-dimensional weights: kaiming-normal over the fan-in.  Every

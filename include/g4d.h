@@ -671,6 +671,24 @@ int g4d_mgn_skin_f32(int clips, int frames_per_clip, int vg, int v, int j, const
                      const float *W, const float *inv_A, const float *A, int *nn_idx, float *nn_dist, float *stage1, float *posed,
                      g4d_stream_t stream);
 
+/* Adjoint of g4d_mgn_skin_f32 with respect to `garment` for a FIXED nearest index (csrc/mgn_skin_grad.hip), one launch: what MGN training
+ * (train_temporal.py --MGN 1) needs to carry the loss gradient from the posed garment back to the displacement MLP.  The index is a
+ * piecewise-constant function of the input; torch's autograd treats it as a constant in the reference too (knn_points(...).idx, torch.gather).
+ * Per (frame f, garment vertex g), nn = nn_idx[f,g] CLAMPED into [0, V-1] (a stale index gives a wrong number, never an out-of-range read):
+ *   M_inv = sum_j W[f,nn,j] inv_A[f,j],  M = sum_j W[f,nn,j] A[f,j]     (the 3x3 parts only: the translation columns and `root` drop out)
+ *   t           = M[:3,:3]^T d_posed[f,g] + d_stage1[f,g]               (d_stage1 == NULL: zero)
+ *   d_garment[f,g] = M_inv[:3,:3]^T t
+ * Summation order: every entry of M_inv / M as in the forward, acc = fma(W[f,nn,j], T_j[r][k], acc) for j = 0, 1, ..., J-1 from acc = 0;
+ * the transposed products are  t[k] = fma(M[2][k], d2, fma(M[1][k], d1, fma(M[0][k], d0, d_stage1[k])))  and
+ * d_garment[k] = fma(M_inv[2][k], t2, fma(M_inv[1][k], t1, M_inv[0][k] * t0)).  No atomics: every output element is written once by one
+ * thread, so two runs give the same bits.  The forward stores nothing for this: both blends are recomputed.
+ * nn_idx (F,Vg) int32 (the forward's output); W (F,V,J); inv_A, A (F,J,4,4), 16-byte aligned; d_posed, d_stage1, d_garment (F,Vg,3).
+ * Same domain as the forward: any V >= 1, 1 <= J <= 64, any Vg and frames_per_clip; nothing is launched when clips, frames_per_clip or
+ * Vg is 0. */
+int g4d_mgn_skin_grad_f32(int clips, int frames_per_clip, int vg, int v, int j, const int *nn_idx, const float *W, const float *inv_A,
+                          const float *A, const float *d_posed, const float *d_stage1 /* may be NULL: zero */, float *d_garment,
+                          g4d_stream_t stream);
+
 /* One Jacobi smoothing step of the blended weights over the garment mesh (modules/mesh_encoder.py:385-390):
  * out (F,Vg,C) = S + coeff * (adj (CSR) . S).  out must not alias S (ping-pong two buffers for the 100 steps). */
 int g4d_spmm_axpy_rows_f32(int frames, int vg, int c, const float *S, const int *rowptr, const int *colidx,
