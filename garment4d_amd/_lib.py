@@ -78,6 +78,9 @@ SIGNATURES = {
     "g4d_interpenetration_f32": [_I, _I, _I, _vp, _vp, _vp, _vp, _I, _vp, _vp],
     "g4d_refine_loss_ws_bytes": [_I, _I, _I],
     "g4d_refine_loss_f32": [_I, _I, _I, _I, _vp, _vp, _vp, _vp, _vp, _I, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _F, _F, _F, _F, _I, _vp, _vp, _vp, _vp, _vp],
+    "g4d_stage1_loss_ws_bytes": [_LL, _I, _I, _I, _I],
+    "g4d_stage1_ce_f32": [_LL, _I, _vp, _vp, _F, _vp, _vp, _vp, _vp],
+    "g4d_stage1_garment_f32": [_I, _I, _I, _I, _I, _I, _vp, _vp, _vp, _vp, _vp, _vp, _I, _vp, _vp, _vp, _vp, _vp, _F, _F, _F, _F, _vp, _vp, _vp, _vp, _vp],
     "g4d_mlp_chain_supported": [_I, _vp],
     "g4d_sa_xyz_mlp3_supported": [_I, _I, _I, _I],
     "g4d_sa_xyz_mlp3_f32": [_I, _I, _I, _I, _vp, _vp, _vp, _I, _I, _I, _vp, _I, _vp, _vp, _vp, _I, _vp, _vp, _vp, _I, _vp, _vp, _I, _vp, _I, _I, _vp],
@@ -139,7 +142,7 @@ SIGNATURES = {
 _lib = None
 
 
-RESTYPES = {"g4d_mlp_args_size": ctypes.c_uint, "g4d_col_sum_rows_ws_bytes": ctypes.c_longlong, "g4d_gemm_tn_slice_rows": ctypes.c_longlong, "g4d_gemm_tn_ws_bytes": ctypes.c_longlong, "g4d_sa_table_ws_bytes": ctypes.c_longlong, "g4d_gcn_tile_meta_bytes": ctypes.c_longlong, "g4d_frag_bf16_elems": ctypes.c_longlong, "g4d_lbs_mfma_ws_bytes": ctypes.c_longlong, "g4d_three_nn_pruned_ws_bytes": ctypes.c_longlong, "g4d_temporal_attention_scratch_floats": ctypes.c_size_t, "g4d_temporal_attention_grad_scratch_floats": ctypes.c_size_t, "g4d_pos_encode_grad_ws_bytes": ctypes.c_longlong, "g4d_refine_loss_ws_bytes": ctypes.c_longlong, "g4d_ball_grid_bytes": ctypes.c_size_t, "g4d_ball_query_lanes_qsort_bytes": ctypes.c_size_t}   # everything else returns an int status
+RESTYPES = {"g4d_mlp_args_size": ctypes.c_uint, "g4d_col_sum_rows_ws_bytes": ctypes.c_longlong, "g4d_gemm_tn_slice_rows": ctypes.c_longlong, "g4d_gemm_tn_ws_bytes": ctypes.c_longlong, "g4d_sa_table_ws_bytes": ctypes.c_longlong, "g4d_gcn_tile_meta_bytes": ctypes.c_longlong, "g4d_frag_bf16_elems": ctypes.c_longlong, "g4d_lbs_mfma_ws_bytes": ctypes.c_longlong, "g4d_three_nn_pruned_ws_bytes": ctypes.c_longlong, "g4d_temporal_attention_scratch_floats": ctypes.c_size_t, "g4d_temporal_attention_grad_scratch_floats": ctypes.c_size_t, "g4d_pos_encode_grad_ws_bytes": ctypes.c_longlong, "g4d_refine_loss_ws_bytes": ctypes.c_longlong, "g4d_stage1_loss_ws_bytes": ctypes.c_longlong, "g4d_ball_grid_bytes": ctypes.c_size_t, "g4d_ball_query_lanes_qsort_bytes": ctypes.c_size_t}   # everything else returns an int status
 
 
 class G4DError(RuntimeError):

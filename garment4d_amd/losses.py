@@ -3,7 +3,9 @@
 penalty, each on a HIP kernel.  The nearest vertex comes from the three-nearest-neighbour kernel of the feature-propagation
 layers (ties -> lowest index, like knn_points here), not from a K=1 top-K search.
 `temporal_loss_PCA_LBS` (:147-201), the stage-2 objective of the refinement head, with its analytic gradient w.r.t. the round outputs
-(csrc/refine_loss.hip); `stage2_loss` is the same on plain tensors."""
+(csrc/refine_loss.hip); `stage2_loss` is the same on plain tensors.
+`temporal_loss_PCA` (:60-119), the stage-1 objective of the garment encoder, with its analytic gradient w.r.t. the logits, the PCA coefficients
+and the T-pose garment (csrc/stage1_loss.hip); `stage1_loss` is the same on plain tensors."""
 import numpy as np
 import torch
 
@@ -223,3 +225,178 @@ def temporal_loss_PCA_LBS(output_dict, inputs, body_model, args=None, *, loss_cf
             "only_lbs_acceleration_error": _acceleration_error(lbs_pred, gt, nbatch, T),
             "total_loss": total,
         }
+
+
+# ------------------------------------------------------------------------------------------------------------ the stage-1 objective
+# `temporal_loss_PCA` (smplx/loss/temporal_loss.py:60-119): the function whose total_loss.backward() trains the garment encoder in the
+# reference's first stage.  Values and the analytic gradient w.r.t. the logits, the PCA coefficients and the T-pose garment come from
+# csrc/stage1_loss.hip; targets, the T-pose body, its normals and the nearest-vertex index are constants, as in the reference -- and so is the
+# cotangent Laplacian, which the reference rebuilds from the predicted vertices on every call and holds fixed in its backward.
+STAGE1_LAMBDAS = ("SEM_SEG_LOSS_LAMBDA", "GARMENT_PCA_COEFF_L2_LAMBDA", "GARMENT_L2_LOSS_LAMBDA", "INTERPENETRATION_LOSS_LAMBDA", "GARMENT_LAP_LOSS_LAMBDA")
+STAGE1_VALUES = ("sem_seg_loss", "garment_pca_coeff_l2", "garment_l2_loss", "garment_msre", "interpenetration_loss", "garment_lap_loss")
+_inc_cache = {}
+
+
+def face_incidence(faces3, vg, device):
+    """The operands of g4d_stage1_garment_f32 for the triangle array `faces3` (nf, 3) (the model's output_dict['garment_f_3']): (faces int32
+    (nf, 3), inc_rowptr (vg + 1), inc) on `device`, inc holding face * 3 + corner for every corner of vertex i between inc_rowptr[i] and
+    inc_rowptr[i + 1], in face order.  Built on the host once per array (cached by identity, like laplacian_csr): not inside a hipGraph capture."""
+    def build():
+        assert torch.device(device).type != "cuda" or not torch.cuda.is_current_stream_capturing(), "face_incidence: build the incidence before the capture (call the loss once eagerly)"
+        f = faces3.detach().cpu().numpy() if torch.is_tensor(faces3) else np.asarray(faces3)
+        f = np.ascontiguousarray(f.reshape(-1, 3).astype(np.int64))
+        assert f.size == 0 or (f.min() >= 0 and f.max() < vg), "a face names a vertex outside the garment"
+        flat = f.reshape(-1)
+        order = np.argsort(flat, kind="stable")                     # entry = face * 3 + corner, ascending within a vertex
+        rowptr = np.zeros(vg + 1, np.int64)
+        np.cumsum(np.bincount(flat, minlength=vg), out=rowptr[1:])
+        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a).astype(np.int32)).to(device)
+        return dev(f), dev(rowptr), dev(order)
+
+    return _cache.by_identity(_inc_cache, 8, (faces3,), (int(vg), str(device)), build)
+
+
+def _stage1_lambdas(loss_cfg):
+    get = (lambda k: loss_cfg[k]) if isinstance(loss_cfg, dict) else (lambda k: getattr(loss_cfg, k))
+    return tuple(float(get(k)) for k in STAGE1_LAMBDAS)
+
+
+def _evaluate_stage1(logits, coeff, pred, want, consts):
+    """The launches of csrc/stage1_loss.hip.  Returns (vals (6,) in STAGE1_VALUES order, [d total / d logits, d coeff, d pred] or None each)."""
+    labels, coeff_gt, target, root, body_v, body_vn, inc, pad_batch, weights, only_seg = consts
+    dev = logits.device
+    st = _lib.stream_ptr()
+    L = _lib.lib()
+    vals = torch.zeros(6, dtype=torch.float32, device=dev)
+    x = logits.detach().float().contiguous()
+    C = x.shape[-1]
+    rows = x.numel() // C if C else 0
+    assert labels.numel() == rows, "one label per row of logits"
+    g_logits = torch.empty_like(x) if want[0] else None
+    ws = torch.empty(max(int(L.g4d_stage1_loss_ws_bytes(rows, 0, 0, 0, 0)) // 4, 1), dtype=torch.float32, device=dev)
+    _lib.call("g4d_stage1_ce_f32", rows, C, x.data_ptr(), labels.data_ptr(), weights[0], ws.data_ptr(), vals.data_ptr(),
+              0 if g_logits is None else g_logits.data_ptr(), st)
+    if only_seg:
+        return vals, [g_logits, None, None]
+    a, p = coeff.detach().float().contiguous(), pred.detach().float().contiguous()
+    B, Vg, _ = p.shape
+    V, P = body_v.shape[1], a.shape[1]
+    faces, rowptr, entries = inc
+    nf = faces.shape[0]
+    q = p + root[:, None, :]
+    idx = fused.three_nn(q, body_v)[1] if B * Vg else torch.zeros((B, Vg, 3), dtype=torch.int32, device=dev)
+    g_coeff = torch.empty_like(a) if want[1] else None
+    g_pred = torch.empty_like(p) if want[2] else None
+    ws = torch.empty(max(int(L.g4d_stage1_loss_ws_bytes(0, B, Vg, nf, int(want[2]))) // 4, 1), dtype=torch.float32, device=dev)
+    out = torch.empty(5, dtype=torch.float32, device=dev)
+    _lib.call("g4d_stage1_garment_f32", B, pad_batch, Vg, V, nf, P, p.data_ptr(), target.data_ptr(), root.data_ptr(), body_v.data_ptr(), body_vn.data_ptr(),
+              idx.data_ptr(), 3, faces.data_ptr(), rowptr.data_ptr(), entries.data_ptr(), a.data_ptr(), coeff_gt.data_ptr(), weights[1], weights[2],
+              weights[3], weights[4], ws.data_ptr(), out.data_ptr(), 0 if g_pred is None else g_pred.data_ptr(),
+              0 if g_coeff is None else g_coeff.data_ptr(), st)
+    vals[1], vals[2:6] = out[4], out[0:4]
+    return vals, [g_logits, g_coeff, g_pred]
+
+
+def _stage1_total(vals, weights, only_seg):
+    """The reference's accumulation order (the MSRE, vals[3], is reported but not part of the total)."""
+    total = vals[0] * weights[0]
+    if only_seg:
+        return total
+    return (((total + vals[1] * weights[1]) + vals[2] * weights[2]) + vals[4] * weights[3]) + vals[5] * weights[4]
+
+
+class _Stage1LossFn(torch.autograd.Function):
+    """total_loss over (logits, coefficients, T-pose garment): the forward evaluates the objective and keeps the gradients of the inputs that
+    require grad; the backward hands each its stored gradient times the incoming scalar."""
+
+    @staticmethod
+    def forward(ctx, consts, logits, coeff, pred):
+        want = [bool(n) for n in ctx.needs_input_grad[1:]]
+        vals, grads = _evaluate_stage1(logits, coeff, pred, want, consts)
+        ctx.want = [w and g is not None for w, g in zip(want, grads)]
+        ctx.shapes = [None if t is None else t.shape for t in (logits, coeff, pred)]
+        ctx.save_for_backward(*[g for g, w in zip(grads, ctx.want) if w])
+        ctx.mark_non_differentiable(vals)
+        return _stage1_total(vals, consts[8], consts[9]), vals
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_total, _g_vals):
+        saved = iter(ctx.saved_tensors)
+        return (None,) + tuple((next(saved) * g_total).reshape(s) if w else None for w, s in zip(ctx.want, ctx.shapes))
+
+
+def stage1_loss(sem_logits, labels, coeff, coeff_gt, tpose_garment, garment_gt, root, body_v, body_vn, faces3, pad_batch, weights, only_seg=False):
+    """The objective on tensors: sem_logits (..., C) point-major with one int label per row; coeff / coeff_gt (B, P); tpose_garment / garment_gt
+    (B, Vg, 3); root (B, 3) the T-pose root joints; body_v / body_vn (B, V, 3) the T-pose body and its unit normals; faces3 (nf, 3) the garment's
+    triangles (see face_incidence); pad_batch >= B the batch size the Laplacian term is padded to with copies of item 0; weights = the five
+    lambdas in STAGE1_LAMBDAS order.  With only_seg only sem_logits and labels are read.  Returns (total, vals (6,) in STAGE1_VALUES order,
+    zeros behind the first under only_seg); `total` carries the graph when grad is enabled and one of sem_logits, coeff, tpose_garment requires
+    grad, `vals` never does.  Without grad: the same launches without gradient buffers, the same bits."""
+    weights = tuple(float(w) for w in weights)
+    assert len(weights) == 5
+    consts_in = (("labels", labels),) if only_seg else (("labels", labels), ("coeff_gt", coeff_gt), ("garment_gt", garment_gt), ("root", root),
+                                                        ("body_v", body_v), ("body_vn", body_vn))
+    if torch.is_grad_enabled():
+        for name, t in consts_in:
+            if t.requires_grad:
+                raise NotImplementedError(f"stage-1 loss: {name} requires grad -- only the logits, the PCA coefficients and the T-pose garment are "
+                                          "differentiated (targets, body vertices and normals are constants of the graph, as in the reference's first stage)")
+    dev = sem_logits.device
+    with torch.no_grad():
+        labels = labels.detach().to(dev).reshape(-1).long().contiguous()
+        if only_seg:
+            consts = (labels, None, None, None, None, None, None, 0, weights, True)
+            coeff = tpose_garment = None
+        else:
+            coeff_gt, garment_gt, root, body_v, body_vn = (t.detach().to(dev).float().contiguous() for t in (coeff_gt, garment_gt, root, body_v, body_vn))
+            B, Vg, _ = tpose_garment.shape
+            assert garment_gt.shape == (B, Vg, 3) and root.shape == (B, 3) and body_v.shape == body_vn.shape and body_v.shape[0] == B
+            assert coeff.shape == coeff_gt.shape and coeff.shape[0] == B and int(pad_batch) >= B, "pad_batch (args.batch_size) is at least the batch"
+            consts = (labels, coeff_gt, garment_gt, root, body_v, body_vn, face_incidence(faces3, Vg, dev), int(pad_batch), weights, False)
+    leaves = [t for t in (sem_logits, coeff, tpose_garment) if t is not None]
+    if torch.is_grad_enabled() and any(t.requires_grad for t in leaves):
+        return _Stage1LossFn.apply(consts, sem_logits, coeff, tpose_garment)
+    with torch.no_grad():
+        vals, _ = _evaluate_stage1(sem_logits, coeff, tpose_garment, [False] * 3, consts)
+        return _stage1_total(vals, weights, only_seg), vals
+
+
+def temporal_loss_PCA(output_dict, inputs, body_model, args, *, loss_cfg):
+    """The reference's four positional arguments (`args.only_seg` and `args.batch_size` are read) plus loss_cfg: anything with the five lambdas
+    of STAGE1_LAMBDAS as attributes (cfg.LOSS) or a dict.  Reads output_dict['sem_logits' | 'garment_PCA_coeff' | 'tpose_garment' | 'garment_f_3']
+    and inputs['pose_torch' | 'pcd_label_torch' | 'PCACoeff' | 'garment_template_vertices' | 'Tpose_smpl_vertices_torch' |
+    'Tpose_smpl_root_joints_torch']; returns the reference's loss_dict keys (the first and the last only with args.only_seg).  The numbers of
+    points, classes and PCA coefficients come from the tensors' shapes.  `total_loss` is differentiable w.r.t. the logits, the coefficients and
+    the T-pose garment (one autograd node on csrc/stage1_loss.hip); every other entry is a detached figure."""
+    weights = _stage1_lambdas(loss_cfg)
+    logits = output_dict["sem_logits"]
+    dev = logits.device
+    B = inputs["pose_torch"].shape[0]
+    if getattr(args, "only_seg", False):
+        total, vals = stage1_loss(logits, inputs["pcd_label_torch"], None, None, None, None, None, None, None, None, 0, weights, only_seg=True)
+        return {"sem_seg_loss": vals[0], "total_loss": total}
+    if torch.is_grad_enabled():
+        for k in ("PCACoeff", "garment_template_vertices", "Tpose_smpl_vertices_torch", "Tpose_smpl_root_joints_torch"):
+            if inputs[k].requires_grad:
+                raise NotImplementedError(f"temporal_loss_PCA: inputs['{k}'] requires grad -- only the logits, the PCA coefficients and the T-pose "
+                                          "garment are differentiated")
+    with torch.no_grad():
+        body_v = inputs["Tpose_smpl_vertices_torch"].to(dev).reshape(B, -1, 3).float().contiguous()
+        root = inputs["Tpose_smpl_root_joints_torch"].to(dev).reshape(B, 3).float()
+        assert body_model.faces.shape[1] == 3 and body_v.shape[1] >= 3, "body needs triangle faces and >= 3 vertices"
+        key = id(body_model)
+        if key not in _vf:
+            fid, vid = mesh_utils.calc_body_mesh_info(body_model)
+            _vf.clear()
+            _vf[key] = (fid.cuda(), vid.cuda(), torch.from_numpy(np.asarray(body_model.faces).astype(np.int64)).cuda())
+        fid, vid, faces = _vf[key]
+        body_vn = mesh_utils.compute_vnorms(body_v, faces, vid, fid)
+    coeff = output_dict["garment_PCA_coeff"].reshape(B, -1)
+    pred = output_dict["tpose_garment"].reshape(B, -1, 3)
+    total, vals = stage1_loss(logits, inputs["pcd_label_torch"], coeff, inputs["PCACoeff"].reshape(B, -1), pred,
+                              inputs["garment_template_vertices"].reshape(B, -1, 3), root, body_v, body_vn, output_dict["garment_f_3"],
+                              int(args.batch_size), weights)
+    out = {k: vals[i] for i, k in enumerate(STAGE1_VALUES)}
+    out["total_loss"] = total
+    return out

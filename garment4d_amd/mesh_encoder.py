@@ -13,6 +13,8 @@ Inference only -- except PCALBSGarmentUseSegEnc
 on: the reference's second training stage (encoder, normals and skinning under no_grad, the refinement head under grad; the objective is
 losses.temporal_loss_PCA_LBS), and PCALBSGarmentUseSegEncoderSegMGN.forward under grad with tuning.Tuning.mgn_autograd on: the reference's MGN training
 (train_temporal.py --MGN 1; encoder under no_grad, the displacement MLP and the nearest-vertex skinning under grad, the same objective).
+Of the first stage only PCAGarmentEncoderSeg.PCA_inverse_transform runs under grad (tuning.Tuning.stage1_autograd; the objective is
+losses.temporal_loss_PCA); PCAGarmentEncoderSeg.forward keeps its assert.
 What the constructor needs from disk in the reference (the PCA basis pickle
 and the garment template OBJ, both part of the CLOTH3D-derived data set that is not available here) can be given either
 through the reference's cfg (`cfg.GARMENT.PCACOMPONENTSFILE`, `cfg.GARMENT.TEMPLATE`) or as arrays.  Frames may be
@@ -67,6 +69,23 @@ def _pack_plain_stack(seq):
     return _cache.packed(seq, "packed", list(seq.parameters()) + list(seq.buffers()), build)
 
 
+class _PCADecodeFn(torch.autograd.Function):
+    """PCA_inverse_transform under grad (tuning.stage1_autograd): the forward is the packed layer launch of the inference route (same bits);
+    the backward is d_out . (components * scale)^T on grad_ops.linear_t.  The PCA basis is a constant."""
+
+    @staticmethod
+    def forward(ctx, coeff, layer, comp, scale):
+        ctx.comp, ctx.scale = comp, scale
+        return fused.linear(coeff.detach().float().contiguous(), layer)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_out):
+        sc = ctx.scale.float().reshape(-1).expand(ctx.comp.shape[1])
+        weight = (ctx.comp.float() * sc[None, :]).t()                     # the Linear weight (3 Vg, pca_dim) of the decode
+        return grad_ops.linear_t(d_out.float().contiguous(), weight), None, None, None
+
+
 class PCAGarmentEncoderSeg(nn.Module):
     def __init__(self, cfg=None, args=None, *, garment_name=None, pca_dim=None, pca=None, template=None, only_seg=None):
         """cfg/args as in the reference, or: garment_name, pca_dim, pca = dict(components (>=pca_dim, 3*Vg), mean (3*Vg,),
@@ -118,6 +137,9 @@ class PCAGarmentEncoderSeg(nn.Module):
 
     def PCA_inverse_transform(self, coeff):
         assert coeff.shape[1] == self.pca_dim
+        if tuning.current().stage1_autograd and torch.is_grad_enabled() and coeff.requires_grad:
+            layer = self._pca_layer(coeff.device)
+            return _PCADecodeFn.apply(coeff, layer, self.PCA_comp, self.PCA_scale).reshape(coeff.shape[0], -1, 3)
         return fused.linear(coeff.float().contiguous(), self._pca_layer(coeff.device)).reshape(coeff.shape[0], -1, 3)   # one MFMA layer launch
 
     def calc_segmentation_results(self, x, sem_logits, n, nbatch, T, feature_pm):

@@ -258,6 +258,40 @@ def stage2_loss_checksum(case):
     return np.array([float(np.asarray(a, dtype=np.float64).sum()) for a in items])
 
 
+def stage1_loss_case(seed=210, N=256, C=7, P=64, pad_batch=4):
+    """The inputs of tests/golden/stage1_loss.npz (written by tests/golden/make_golden_stage1_loss.py, which runs the reference's own
+    `temporal_loss_PCA` on them): the T-pose body and the 64-vertex quad-cylinder template of refine_golden_case with its quads split into
+    triangles (`garment_f_3`), logits of a few units for nbatch * T * N points with labels over all C classes, P PCA coefficients and targets,
+    a `tpose_garment` placed around the T-pose body (garment_around_body; garment vertex i follows body vertex sel[i]) minus the root joint,
+    `garment_template_vertices` = tpose_garment + N(0, 0.01), and args.batch_size = pad_batch > nbatch, so that the Laplacian term's padding
+    with copies of item 0 is exercised.  stage1_loss_checksum() guards against generator drift."""
+    base = refine_golden_case()
+    nbatch, T, Vg = base["nbatch"], base["T"], base["Vg"]
+    rng = np.random.default_rng(seed)
+    body_v = base["batch"]["Tpose_smpl_vertices_torch"].reshape(nbatch, -1, 3)
+    root = base["batch"]["Tpose_smpl_root_joints_torch"].reshape(nbatch, 1, 3)
+    body_n = vertex_normals(body_v, base["body"]["faces"])
+    sel = rng.permutation(body_v.shape[1])[:Vg]
+    tpose_garment = (garment_around_body(rng, body_v, body_n, sel) - root).astype(F32)
+    template = (tpose_garment + rng.normal(0.0, 0.01, (nbatch, Vg, 3))).astype(F32)
+    quads = base["template_faces"]
+    faces3 = np.concatenate([[q[[0, 1, 2]], q[[0, 2, 3]]] for q in quads], 0).astype(np.int32)      # mesh_utils.quads2tris
+    logits = (rng.standard_normal((nbatch * T, N, C)) * 2.0).astype(F32)
+    labels = rng.integers(0, C, (nbatch, T, N)).astype(np.int64)
+    coeff = rng.standard_normal((nbatch, P)).astype(F32)
+    coeff_gt = (coeff + rng.normal(0.0, 0.3, (nbatch, P))).astype(F32)
+    return dict(seed=seed, nbatch=nbatch, T=T, N=N, C=C, P=P, Vg=Vg, pad_batch=pad_batch, body=base["body"],
+                output=dict(sem_logits=logits, garment_PCA_coeff=coeff, tpose_garment=tpose_garment, garment_f_3=faces3),
+                inputs=dict(pose_torch=base["batch"]["pose_torch"], pcd_label_torch=labels, PCACoeff=coeff_gt, garment_template_vertices=template,
+                            Tpose_smpl_vertices_torch=base["batch"]["Tpose_smpl_vertices_torch"],
+                            Tpose_smpl_root_joints_torch=base["batch"]["Tpose_smpl_root_joints_torch"]))
+
+
+def stage1_loss_checksum(case):
+    items = [v for _, v in sorted(case["output"].items())] + [v for _, v in sorted(case["inputs"].items())]
+    return np.array([float(np.asarray(a, dtype=np.float64).sum()) for a in items])
+
+
 def mgn_displacement_state_dict(vg, seed=0):
     """Seeded weights under the reference's names for the MGN variant's `displacement_encoder` (modules/mesh_encoder.py:518-524:
     Linear 512 -> 1024 -> 2048 -> 3 vg), drawn like torch's default Linear initialisation (uniform +-1/sqrt(in)).  numpy, fp32."""

@@ -784,6 +784,37 @@ int g4d_refine_loss_f32(int nbatch, int t, int vg, int v, const float *pred, con
                         const int *rowptr_t, const int *colidx_t, const float *vals_t, float w_l2, float w_lap, float w_pen, float w_temporal,
                         int temporal, float *ws, float *out, float *msre_frames, float *grad, g4d_stream_t stream);
 
+/* The stage-1 objective of the garment encoder (smplx/loss/temporal_loss.py:60-119 `temporal_loss_PCA`; csrc/stage1_loss.hip, which writes
+ * out the arithmetic and the reduction trees).  No atomics; the order of every sum depends on the shape alone: two runs give the same bits,
+ * with or without gradient buffers.
+ *
+ * g4d_stage1_loss_ws_bytes: the workspace of either entry point, or of both when they share one buffer one after the other:
+ *   4 * (ceil(ce_rows / 256)  +  [b > 0 && vg > 0] (b ceil(vg / 256) 4 + 2 b nf 3 + [with_grad] b vg 3)).
+ *
+ * g4d_stage1_ce_f32: out (1) = the mean over `rows` rows of  log sum_c exp(x_c) - x_label  (torch's CrossEntropyLoss(), mean), logits
+ * (rows, classes) row-major, 1 <= classes <= 64, labels int64.  grad (rows, classes) or NULL (value only): fully written with
+ * w_sem d out[0] / d logits = (w_sem / rows) (softmax - onehot).  A label outside [0, classes) is never used as an index: out[0] is NaN and
+ * the row's gradient zero (torch's ignore_index would drop the row from the mean; not implemented).  rows may exceed 2^31 - 1 (64-bit
+ * offsets).  ws: g4d_stage1_loss_ws_bytes(rows, 0, 0, 0, 0) bytes.  rows == 0: out = 0, nothing else is touched.
+ *
+ * g4d_stage1_garment_f32: pred / target (b, vg, 3) the predicted T-pose garment and its target; root (b, 3) added to pred for the
+ * penetration term; body / normals (b, v, 3); nn_idx int32 with idx_stride ints per garment vertex, the first being the nearest body vertex
+ * of pred + root (the output of g4d_three_nn_f32: idx_stride 3); faces (nf, 3) int32 triangles over the vg vertices; (inc_rowptr (vg + 1),
+ * inc) the vertex -> incidence CSR, each entry = face * 3 + corner with faces[entry] == the vertex; coeff / coeff_gt (b, pdim).
+ * out (5) = [mean |p-g|^2, mean |p-g|, mean relu(-n_b.(p+root-b)), the one-time cotangent-Laplacian term
+ * mean_{item < bp, i} | |(L(p) p)_i| - |(L(g) g)_i| | with the items b..bp-1 being copies of item 0 (a weight 1 + bp - b on item 0; nothing is
+ * copied), mean (coeff - coeff_gt)^2].  grad_pred (b, vg, 3) or NULL: fully written with w_l2 d out[0] + w_pen d out[2] + w_lap d out[3]
+ * w.r.t. pred, L held constant as in the reference's backward; a face of zero area has zero cotangents, a vertex with |(L p)_i| = 0 or
+ * = |(L g)_i| contributes zero.  grad_coeff (b, pdim) or NULL: w_pca d out[4] / d coeff.  A weight of 0 leaves its value reported.
+ * ws: g4d_stage1_loss_ws_bytes(0, b, vg, nf, grad_pred != NULL) bytes.  b == 0 or vg == 0: out = zeros, nothing else is touched. */
+long long g4d_stage1_loss_ws_bytes(long long ce_rows, int b, int vg, int nf, int with_grad);
+int g4d_stage1_ce_f32(long long rows, int classes, const float *logits, const long long *labels, float w_sem, float *ws, float *out, float *grad,
+                      g4d_stream_t stream);
+int g4d_stage1_garment_f32(int b, int bp, int vg, int v, int nf, int pdim, const float *pred, const float *target, const float *root,
+                           const float *body, const float *normals, const int *nn_idx, int idx_stride, const int *faces, const int *inc_rowptr,
+                           const int *inc, const float *coeff, const float *coeff_gt, float w_pca, float w_l2, float w_pen, float w_lap, float *ws,
+                           float *out, float *grad_pred, float *grad_coeff, g4d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
