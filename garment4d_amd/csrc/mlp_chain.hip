@@ -553,7 +553,8 @@ static int chain_launch_one(int mode, int key, int mt, const ChainArgs &s, hipSt
         case 8160000: G4D_CHAIN(8, 16, 0, 0)
         case 4080000: G4D_CHAIN(4, 8, 0, 0)
         case 16080800: G4D_CHAIN(16, 8, 8, 0)
-        default: G4D_CHAIN(8, 4, 2, 1)
+        case 8040201: G4D_CHAIN(8, 4, 2, 1)
+        default: G4D_REQUIRE(false, "g4d_mlp_chain_f32: no instantiation for these widths (key %d)", key);
 #else
         case 1010200: G4D_CHAIN(1, 1, 2, 0)
         case 2020400: G4D_CHAIN(2, 2, 4, 0)
@@ -574,7 +575,8 @@ static int chain_launch_one(int mode, int key, int mt, const ChainArgs &s, hipSt
         case 2040000: G4D_CHAIN(2, 4, 0, 0)
         case 4080000: G4D_CHAIN(4, 8, 0, 0)
         case 8160000: G4D_CHAIN(8, 16, 0, 0)
-        default: G4D_CHAIN(8, 4, 2, 1)
+        case 8040201: G4D_CHAIN(8, 4, 2, 1)
+        default: G4D_REQUIRE(false, "g4d_mlp_chain_f32: no instantiation for these widths (key %d)", key);
 #endif
     }
 #undef G4D_CHAIN

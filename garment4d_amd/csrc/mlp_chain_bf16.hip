@@ -503,7 +503,8 @@ static int chain_bf16_impl(const char *name, int nspl, int mode, long long rows,
         case 2000000: G4D_CHAIN(2, 0, 0, 0)
         case 4000000: G4D_CHAIN(4, 0, 0, 0)
         case 8000000: G4D_CHAIN(8, 0, 0, 0)
-        default: G4D_CHAIN(8, 4, 2, 1)
+        case 8040201: G4D_CHAIN(8, 4, 2, 1)
+        default: G4D_REQUIRE(false, "%s: no bf16 instantiation for these widths (key %d)", name, key);   // returned before any launch
     }
 #undef G4D_CHAIN
     return check_launch(name);

@@ -313,12 +313,20 @@ _CHAIN_TILES = {(1, 1, 2), (2, 2, 4), (4, 4, 8), (8, 8, 16), (2, 2), (4, 4), (8,
                 (4, 2, 1), (2, 4), (4, 8), (8, 16), (16,), (16, 8, 8)}
 
 
-def chain_fits(layers, pool, S, mode):
+# ... and the ones csrc/mlp_chain_bf16.hip instantiates (the case labels of the switch in chain_bf16_impl, "bf16" and "bf16x3" alike): the
+# widths of the default routes in those precisions.  Anything else takes the LDS stack kernel ("bf16") or the fp32 chain kernel ("bf16x3").
+_CHAIN_TILES_BF16 = {(1, 1, 2), (2, 2, 4), (4, 4, 8), (8, 8, 16), (2, 2), (4, 4), (8, 8), (8, 4), (16, 8), (1,), (2,), (4,), (8,), (8, 4, 2, 1)}
+
+
+def chain_fits(layers, pool, S, mode, bf16=None):
     """Register-resident chain kernel (csrc/mlp_chain.hip): DIRECT / GROUP loader, 1..3 layers whose 16-channel tile counts
-    are one of the instantiated combinations (mirrors g4d_mlp_chain_supported)."""
+    are one of the instantiated combinations (mirrors g4d_mlp_chain_supported).  bf16=True asks for the bf16-operand kernel
+    (csrc/mlp_chain_bf16.hip, fewer instantiations); None = the kernel the precision in force would run."""
     if not _T().use_chain or mode not in (0, 1, 2) or (pool and S not in _POOL_WINDOWS):
         return False
-    return tuple((L.Cout + 15) // 16 for L in layers) in _CHAIN_TILES
+    if bf16 is None:
+        bf16 = current_precision() == "bf16"
+    return tuple((L.Cout + 15) // 16 for L in layers) in (_CHAIN_TILES_BF16 if bf16 else _CHAIN_TILES)
 
 
 def wave_fits(layers, pool, S):
@@ -370,15 +378,15 @@ def mlp_stack(mode, rows, K0, layers, out, col0=0, pool=0, S=1, X=None, ldx=0, g
         _lib.call("g4d_mlp_run", family, ctypes.pointer(a), _lib.stream_ptr())
         return out
 
-    if current_precision() == "bf16" and chain_fits(layers, pool, S, mode):   # register-chain bf16 kernel: any launch size, no LDS
+    if current_precision() == "bf16" and chain_fits(layers, pool, S, mode, bf16=True):   # register-chain bf16 kernel: any launch size, no LDS
         if mode == 2 and cells_grid is not None:
             a.unknown_grid = cells_grid.data_ptr()       # rows walked in the cell order of the unknown cloud's grid (same bits)
         return run(_lib.MLP_CHAIN_BF16, PA(*[L.Wc16.data_ptr() for L in layers]))
-    if current_precision() == "bf16x3" and chain_fits(layers, pool, S, mode):
+    if current_precision() == "bf16x3" and chain_fits(layers, pool, S, mode, bf16=True):
         return run(_lib.MLP_CHAIN_BF16X3, (ctypes.c_void_p * (3 * n))(*[t.data_ptr() for L in layers for t in L.Wc16x3()]))
     if _use_bf16(rows):
         return run(_lib.MLP_STACK_BF16, PA(*[L.Wf16.data_ptr() for L in layers]))
-    if current_precision() in ("fp32", "bf16x3") and chain_fits(layers, pool, S, mode):
+    if current_precision() in ("fp32", "bf16x3") and chain_fits(layers, pool, S, mode, bf16=False):
         return run(_lib.MLP_CHAIN_F32, Wp)
     if tap is None and wave_fits(layers, pool, S):
         return run(_lib.MLP_WAVE_F32, Wp)
