@@ -47,6 +47,14 @@ SIGNATURES = {
     "g4d_mlp_wave_f32": [_I, _LL, _I, _vp, _I, _I, _I, _I, _I, _I, _vp, _vp, _vp, _vp, _I, _I, _I, _I, _vp, _vp, _vp, _vp,
                          _I, _vp, _vp, _vp, _I, _vp, _vp, _vp, _vp, _vp, _vp, _I, _vp, _I, _I, _vp],
     "g4d_pool_rows_f32": [_I, _I, _I, _vp, _I, _vp, _I, _I, _I, _vp],
+    "g4d_bn_slice_rows": [_LL, _I],
+    "g4d_bn_stats_ws_bytes": [_LL, _I],
+    "g4d_bn_stats_f32": [_LL, _I, _vp, _I, _vp, _vp, _vp, _vp],
+    "g4d_bn_act_f32": [_LL, _I, _vp, _I, _vp, _vp, _F, _vp, _vp, _I, _vp, _I, _vp],
+    "g4d_bn_act_grad_reduce_ws_bytes": [_LL, _I],
+    "g4d_bn_act_grad_reduce_f32": [_LL, _I, _vp, _I, _vp, _I, _vp, _vp, _F, _vp, _vp, _I, _vp, _vp, _vp, _vp],
+    "g4d_bn_act_grad_f32": [_LL, _I, _vp, _I, _vp, _I, _vp, _vp, _F, _vp, _vp, _I, _I, _vp, _vp, _vp, _I, _vp],
+    "g4d_pool_rows_max_grad_f32": [_I, _I, _I, _vp, _I, _vp, _I, _I, _vp, _vp],
     "g4d_transpose_f32": [_I, _I, _I, _vp, _vp, _vp],
     "g4d_copy_segments_f32": [_I, _vp, _vp, _vp, _vp],
     "g4d_linear_interp_add_f32": [_LL, _I, _I, _I, _I, _I, _vp, _I, _vp, _vp, _I, _vp, _vp, _vp, _vp, _I, _vp, _I, _I, _vp],
@@ -142,7 +150,7 @@ SIGNATURES = {
 _lib = None
 
 
-RESTYPES = {"g4d_mlp_args_size": ctypes.c_uint, "g4d_col_sum_rows_ws_bytes": ctypes.c_longlong, "g4d_gemm_tn_slice_rows": ctypes.c_longlong, "g4d_gemm_tn_ws_bytes": ctypes.c_longlong, "g4d_sa_table_ws_bytes": ctypes.c_longlong, "g4d_gcn_tile_meta_bytes": ctypes.c_longlong, "g4d_frag_bf16_elems": ctypes.c_longlong, "g4d_lbs_mfma_ws_bytes": ctypes.c_longlong, "g4d_three_nn_pruned_ws_bytes": ctypes.c_longlong, "g4d_temporal_attention_scratch_floats": ctypes.c_size_t, "g4d_temporal_attention_grad_scratch_floats": ctypes.c_size_t, "g4d_pos_encode_grad_ws_bytes": ctypes.c_longlong, "g4d_refine_loss_ws_bytes": ctypes.c_longlong, "g4d_stage1_loss_ws_bytes": ctypes.c_longlong, "g4d_ball_grid_bytes": ctypes.c_size_t, "g4d_ball_query_lanes_qsort_bytes": ctypes.c_size_t}   # everything else returns an int status
+RESTYPES = {"g4d_mlp_args_size": ctypes.c_uint, "g4d_bn_slice_rows": ctypes.c_longlong, "g4d_bn_stats_ws_bytes": ctypes.c_longlong, "g4d_bn_act_grad_reduce_ws_bytes": ctypes.c_longlong, "g4d_col_sum_rows_ws_bytes": ctypes.c_longlong, "g4d_gemm_tn_slice_rows": ctypes.c_longlong, "g4d_gemm_tn_ws_bytes": ctypes.c_longlong, "g4d_sa_table_ws_bytes": ctypes.c_longlong, "g4d_gcn_tile_meta_bytes": ctypes.c_longlong, "g4d_frag_bf16_elems": ctypes.c_longlong, "g4d_lbs_mfma_ws_bytes": ctypes.c_longlong, "g4d_three_nn_pruned_ws_bytes": ctypes.c_longlong, "g4d_temporal_attention_scratch_floats": ctypes.c_size_t, "g4d_temporal_attention_grad_scratch_floats": ctypes.c_size_t, "g4d_pos_encode_grad_ws_bytes": ctypes.c_longlong, "g4d_refine_loss_ws_bytes": ctypes.c_longlong, "g4d_stage1_loss_ws_bytes": ctypes.c_longlong, "g4d_ball_grid_bytes": ctypes.c_size_t, "g4d_ball_query_lanes_qsort_bytes": ctypes.c_size_t}   # everything else returns an int status
 
 
 class G4DError(RuntimeError):

@@ -55,3 +55,52 @@ def linear_t(ds2d, weight):
         L = fused.PackedLayer(weight.detach().float().t().contiguous(), torch.ones(cin, device=weight.device),
                               torch.zeros(cin, device=weight.device), relu=False)
     return fused.linear(ds2d, L)
+
+
+def _ws(nbytes, device):
+    return torch.empty(max(int(nbytes) // 4, 1), dtype=torch.float32, device=device)
+
+
+def bn_stats(rows, c, y, ldy):
+    """(mean, biased variance), each (c,), over the rows of the first c columns of y (rows ldy >= c apart): g4d_bn_stats_f32, two passes, slice
+    partials added in a fixed order."""
+    mean = torch.empty(c, dtype=torch.float32, device=y.device)
+    var = torch.empty(c, dtype=torch.float32, device=y.device)
+    ws = _ws(_lib.lib().g4d_bn_stats_ws_bytes(rows, c), y.device)
+    _lib.call("g4d_bn_stats_f32", rows, c, y.data_ptr(), ldy, ws.data_ptr(), mean.data_ptr(), var.data_ptr(), _lib.stream_ptr())
+    return mean, var
+
+
+def bn_act(rows, c, y, ldy, mean, var, eps, gamma, beta, relu, out=None, ldo=None):
+    """act(gamma * (y - mean) / sqrt(var + eps) + beta), (rows, c): g4d_bn_act_f32.  gamma / beta None: 1 / 0."""
+    if out is None:
+        out, ldo = torch.empty((rows, c), dtype=torch.float32, device=y.device), c
+    _lib.call("g4d_bn_act_f32", rows, c, y.data_ptr(), ldy, mean.data_ptr(), var.data_ptr(), float(eps), fused._ptr(gamma), fused._ptr(beta), int(relu),
+              out.data_ptr(), ldo, _lib.stream_ptr())
+    return out
+
+
+def bn_act_grad_reduce(rows, c, dout, ldg, y, ldy, mean, var, eps, gamma, beta, relu):
+    """(dgamma, dbeta) = (sum G * xhat, sum G) with G = dout where the activation passed: g4d_bn_act_grad_reduce_f32 (mask and xhat recomputed from y)."""
+    dgamma = torch.empty(c, dtype=torch.float32, device=y.device)
+    dbeta = torch.empty(c, dtype=torch.float32, device=y.device)
+    ws = _ws(_lib.lib().g4d_bn_act_grad_reduce_ws_bytes(rows, c), y.device)
+    _lib.call("g4d_bn_act_grad_reduce_f32", rows, c, dout.data_ptr(), ldg, y.data_ptr(), ldy, mean.data_ptr(), var.data_ptr(), float(eps),
+              fused._ptr(gamma), fused._ptr(beta), int(relu), ws.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), _lib.stream_ptr())
+    return dgamma, dbeta
+
+
+def bn_act_grad(rows, c, dout, ldg, y, ldy, mean, var, eps, gamma, beta, relu, batch_stats, dgamma=None, dbeta=None):
+    """dY (rows, c) of act(BatchNorm(Y)): g4d_bn_act_grad_f32.  batch_stats False (running statistics): the two mean terms are dropped and
+    dgamma / dbeta are not read."""
+    dy = torch.empty((rows, c), dtype=torch.float32, device=y.device)
+    _lib.call("g4d_bn_act_grad_f32", rows, c, dout.data_ptr(), ldg, y.data_ptr(), ldy, mean.data_ptr(), var.data_ptr(), float(eps), fused._ptr(gamma),
+              fused._ptr(beta), int(relu), int(batch_stats), fused._ptr(dgamma), fused._ptr(dbeta), dy.data_ptr(), c, _lib.stream_ptr())
+    return dy
+
+
+def pool_rows_max_grad(groups, S, c, x, ldx, dpooled, ldp, col0=0):
+    """dX (groups * S, c) of the row max-pool: dpooled at the first row of each group attaining the maximum, 0 elsewhere: g4d_pool_rows_max_grad_f32."""
+    dx = torch.empty((groups * S, c), dtype=torch.float32, device=x.device)
+    _lib.call("g4d_pool_rows_max_grad_f32", groups, S, c, x.data_ptr(), ldx, dpooled.data_ptr(), ldp, col0, dx.data_ptr(), _lib.stream_ptr())
+    return dx

@@ -10,7 +10,8 @@ forward() has two routes behind the reference's one signature:
     modules/pointnet2encoder.py:127-140 loop, transposes once per level output and never back.
   * everything else (training mode, autograd enabled, CPU / non-fp32 tensors, pre-activation / instance-norm / non-ReLU
     stacks, Tuning.dropin_fused = False): the op-by-op path -- every op a HIP kernel through the drop-in boundary,
-    SharedMLP through torch so that it is trainable, incl. train-mode BatchNorm.
+    SharedMLP through torch so that it is trainable, incl. train-mode BatchNorm -- or, with the opt-in Tuning.mlp_autograd, through the
+    HIP training kernels (mlp_train.py: conv + batch-statistics BatchNorm + ReLU blocks and the max-pool as autograd nodes on rows).
 
 Both routes read the same parameters (same state-dict keys); they agree within fp32 rounding (tests/test_dropin_gpu.py).
 """
@@ -82,6 +83,21 @@ class _PointnetSAModuleBase(nn.Module):
             new_xyz = pointnet2_utils.gather_operation(xyz.transpose(1, 2).contiguous(), sample_idx)
             new_xyz = new_xyz.transpose(1, 2).contiguous()
         pooled = []
+        rows_route = None
+        if self.pool_method == "max_pool":
+            from . import mlp_train
+            if mlp_train.applies(self, xyz, new_xyz, features):   # opt-in (Tuning.mlp_autograd): stack AND pool on point-major rows
+                rows_route = [mlp_train.plain_stack(mlp) for mlp in self.mlps]
+                if any(b is None for b in rows_route):
+                    rows_route = None
+        if rows_route is not None:
+            hs, Ss = [], []
+            for grouper, blocks in zip(self.groupers, rows_route):
+                g = grouper(xyz, new_xyz, features)   # (B, C, npoint, nsample): to rows once, never back
+                hs.append(mlp_train.run_blocks(blocks, mlp_train.to_rows(g)))
+                Ss.append(g.shape[3])
+            # every scale pooled into its column window of one (B * npoint, sum Cout) matrix; only that goes back to channel-major
+            return new_xyz, mlp_train.to_channels(mlp_train.pool_rows_max(hs, Ss), xyz.shape[0])
         for grouper, mlp in zip(self.groupers, self.mlps):
             h = mlp(grouper(xyz, new_xyz, features))  # (B, Cout, npoint, nsample)
             if self.pool_method == "max_pool":

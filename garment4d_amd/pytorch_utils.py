@@ -1,7 +1,8 @@
 """SharedMLP / Conv1d / Conv2d / FC / BatchNorm containers with the reference's constructor signatures and
 STATE-DICT KEYS (modules/pointnet2/pointnet2/pytorch_utils.py): e.g.
 `layer0.conv.weight (Cout,Cin,1,1)`, `layer0.bn.bn.{weight,bias,running_mean,running_var,num_batches_tracked}`,
-so reference checkpoints load unchanged.  These containers are the trainable (un-fused) path; eval-mode
+so reference checkpoints load unchanged.  These containers are the trainable (un-fused) path -- torch's layers, or with the
+opt-in Tuning.mlp_autograd autograd nodes over the HIP kernels (mlp_train.py, csrc/bn_train.hip) --; eval-mode
 inference goes through the fused HIP kernels (garment4d_amd/fused.py), which read these modules' tensors -- the SA / FP
 modules dispatch there themselves (pointnet2_modules.py), and a `Conv1d` block called on its own in eval() + no_grad (the
 FC head of pointnet2encoder.py:141) runs as one HIP contraction on the input's point-major twin.
@@ -85,6 +86,12 @@ class Conv1d(_ConvBase):
                     pm = fused.point_major_of(x)
                     B, N, C = pm.shape
                     return fused.channel_major_with_twin(fused.linear(pm.view(B * N, C), L).view(B, N, L.Cout))
+        if x.dim() == 3:
+            from . import mlp_train
+            if mlp_train.applies(self, x):      # opt-in (Tuning.mlp_autograd): the block as one autograd node over the HIP kernels
+                blk = mlp_train.plain_block(self)
+                if blk is not None:
+                    return mlp_train.forward_channel_major([blk], x)
         return super().forward(x)
 
 
@@ -109,6 +116,18 @@ class SharedMLP(nn.Sequential):
             self.add_module(name + "layer{}".format(i),
                             Conv2d(args[i], args[i + 1], bn=plain and bn, activation=activation if plain else None,
                                    preact=preact, instance_norm=instance_norm))
+
+    def forward(self, x):
+        """(B, Cin, N, S) -> (B, Cout, N, S) through torch's layers (trainable, as the reference); with Tuning.mlp_autograd, under grad or with a
+        BatchNorm in train(), on fp32 HIP tensors and plain 1x1 conv [+ BN] [+ ReLU] blocks: the same function as autograd nodes over the HIP
+        kernels, chained on point-major rows (mlp_train.py)."""
+        if x.dim() == 4:
+            from . import mlp_train
+            if mlp_train.applies(self, x):
+                blocks = mlp_train.plain_stack(self)
+                if blocks is not None:
+                    return mlp_train.forward_channel_major(blocks, x)
+        return super().forward(x)
 
 
 class FC(nn.Sequential):

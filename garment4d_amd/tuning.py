@@ -94,6 +94,10 @@ class Tuning:
                                        #  a tensor with a graph (the same packed layer launch forward, grad_ops.linear_t backward) -- the first node of the
                                        #  stage-1 route, whose objective is losses.temporal_loss_PCA (csrc/stage1_loss.hip); False: no graph, as it always was.
                                        #  PCAGarmentEncoderSeg.forward itself stays inference-only
+    mlp_autograd: bool = False         # pytorch_utils.py / pointnet2_modules.py: SharedMLP / Conv1d / the op-by-op SA level called under grad or with a BatchNorm in
+                                       #  train() run their 1x1 conv (+ BN) (+ ReLU) blocks as autograd nodes over HIP kernels (mlp_train.py: g4d_linear_f32,
+                                       #  csrc/bn_train.hip with batch statistics and the running-statistics bookkeeping, g4d_gemm_tn_f32, g4d_col_sum_rows_f32),
+                                       #  the SA level's max-pool on rows with g4d_pool_rows_max_grad_f32 as its backward; False: torch's layers, as it always was
     # ---- lbs() routes (lbs.py).  NOT bit-identical to each other (different partitions of the blend sum; each within 1e-5 of the reference)
     lbs_fused: bool = True             # False: the five-step path that follows smplx/lbs.py line by line
     lbs_mfma: bool = True              # round 5: matrix-pipe route (g4d_lbs_mfma_f32), taken at every batch size
@@ -134,7 +138,7 @@ def from_environment() -> Tuning:
         fp_gemm_bf16=_env_flag("G4D_FP_GEMM_BF16", d.fp_gemm_bf16), fp_gemm_bf16_min_rows=_env_int("G4D_FP_GEMM_BF16_MIN_ROWS", d.fp_gemm_bf16_min_rows),
         fp_wide_table=_env_flag("G4D_FP_WIDE_TABLE", d.fp_wide_table), gcn_fuse_stack=_env_flag("G4D_GCN_FUSED", d.gcn_fuse_stack), gcn_autograd=_env_flag("G4D_GCN_AUTOGRAD", d.gcn_autograd),
         refine_autograd=_env_flag("G4D_REFINE_AUTOGRAD", d.refine_autograd), mgn_autograd=_env_flag("G4D_MGN_AUTOGRAD", d.mgn_autograd),
-        stage1_autograd=_env_flag("G4D_STAGE1_AUTOGRAD", d.stage1_autograd),
+        stage1_autograd=_env_flag("G4D_STAGE1_AUTOGRAD", d.stage1_autograd), mlp_autograd=_env_flag("G4D_MLP_AUTOGRAD", d.mlp_autograd),
         dropin_fused=_env_flag("G4D_DROPIN_FUSED", d.dropin_fused), dropin_whole_model=_env_flag("G4D_DROPIN_WHOLE", d.dropin_whole_model), lbs_mfma=_env_flag("G4D_LBS_MFMA", d.lbs_mfma), lbs_one_launch=_env_flag("G4D_LBS_ONE", d.lbs_one_launch),
         lbs_one_launch_max_b=_env_int("G4D_LBS_ONE_MAX_B", d.lbs_one_launch_max_b))
 

@@ -31,7 +31,7 @@ typedef struct ihipStream_t *g4d_stream_t; /* == hipStream_t */
 #define G4D_OK 0
 #define G4D_EINVAL 10001 /* bad argument (negative size, null pointer, unsupported width) */
 
-int g4d_version(void); /* 100 * major + minor: 200 = round 2 (the `boxes` scratch of g4d_ball_query_boxes_f32 grew to 16-point sub-blocks); 205 / 206 = round 5 (entry points added, none changed; 206: g4d_gcn_tile_meta_*, g4d_gcn_agg_linear_meta_f32); 260 = round 6 (added: g4d_mlp_run / g4d_mlp_args, g4d_mlp_chain_group_table_ws_f32, g4d_sa_table_ws_bytes, g4d_sa_table_supported; none changed); 261 (entry points added, none changed: g4d_mgn_skin_f32); 262 (entry points added, none changed: g4d_spmm_rows_grad_f32, g4d_col_sum_rows_f32, g4d_gemm_tn_f32 and their size queries); 263 (entry points added, none changed: g4d_pos_encode_grad_f32, g4d_temporal_attention_grad_f32 and their size queries) */
+int g4d_version(void); /* 100 * major + minor: 200 = round 2 (the `boxes` scratch of g4d_ball_query_boxes_f32 grew to 16-point sub-blocks); 205 / 206 = round 5 (entry points added, none changed; 206: g4d_gcn_tile_meta_*, g4d_gcn_agg_linear_meta_f32); 260 = round 6 (added: g4d_mlp_run / g4d_mlp_args, g4d_mlp_chain_group_table_ws_f32, g4d_sa_table_ws_bytes, g4d_sa_table_supported; none changed); 261 (entry points added, none changed: g4d_mgn_skin_f32); 262 (entry points added, none changed: g4d_spmm_rows_grad_f32, g4d_col_sum_rows_f32, g4d_gemm_tn_f32 and their size queries); 263 (entry points added, none changed: g4d_pos_encode_grad_f32, g4d_temporal_attention_grad_f32 and their size queries); later additions that change nothing (g4d_mgn_skin_grad_f32, g4d_stage1_*, g4d_bn_*, g4d_pool_rows_max_grad_f32) keep 263 */
 const char *g4d_last_error(void);
 
 /* ---- numerics: how the squared distance of FPS / ball query / three_nn / knn is rounded ---------------------------------
@@ -391,6 +391,36 @@ int g4d_gemm_tn_f32(long long rows, int fin, int ldx, int cout, const float *X, 
 /* max (is_max=1) / mean over S consecutive rows, any S: in (groups*S, ldi) -> out (groups, ldo) at col0. */
 int g4d_pool_rows_f32(int groups, int s, int c, const float *in, int ldi, float *out, int ldo, int col0, int is_max,
                       g4d_stream_t stream);
+
+/* ---- training-mode BatchNorm on point-major rows, and the adjoint of the row max-pool (csrc/bn_train.hip; garment4d_amd/mlp_train.py) ----
+ * Y (rows, C) with a row stride ld >= C floats, one column = one channel.  fp32; every output is written once; no atomics; the rows are cut
+ * into slices of g4d_bn_slice_rows(rows, c) rows -- a function of the shape alone -- whose partial sums go to ws and are added in slice
+ * order, so two runs give the same bits.  Negative sizes, ld < C and null pointers (where not optional) return G4D_EINVAL before any launch.
+ *
+ * g4d_bn_stats_f32: mean (C) and BIASED variance (C) over the rows, two passes (sum y, then sum (y - mean)^2).  ws: g4d_bn_stats_ws_bytes
+ * bytes.  rows == 0 writes zeros. */
+long long g4d_bn_slice_rows(long long rows, int c);
+long long g4d_bn_stats_ws_bytes(long long rows, int c);
+int g4d_bn_stats_f32(long long rows, int c, const float *Y, int ldy, float *ws, float *mean, float *var, g4d_stream_t stream);
+/* out = act(z), z = fma((y - mean) * invstd, gamma, beta), invstd = 1 / sqrt(var + eps); relu != 0: act(z) = z > 0 ? z : 0.  gamma / beta
+ * NULL: 1 / 0. */
+int g4d_bn_act_f32(long long rows, int c, const float *Y, int ldy, const float *mean, const float *var, float eps, const float *gamma,
+                   const float *beta, int relu, float *out, int ldo, g4d_stream_t stream);
+/* With G = dOut where the activation passed (z > 0, z recomputed from Y by the expression of g4d_bn_act_f32) and 0 elsewhere:
+ * dbeta (C) = sum G, dgamma (C) = sum G * xhat, xhat = (y - mean) * invstd.  ws: g4d_bn_act_grad_reduce_ws_bytes bytes.  rows == 0 writes zeros. */
+long long g4d_bn_act_grad_reduce_ws_bytes(long long rows, int c);
+int g4d_bn_act_grad_reduce_f32(long long rows, int c, const float *dOut, int ldg, const float *Y, int ldy, const float *mean, const float *var,
+                               float eps, const float *gamma, const float *beta, int relu, float *ws, float *dgamma, float *dbeta,
+                               g4d_stream_t stream);
+/* dY = gamma * invstd * (G - dbeta / rows - xhat * dgamma / rows); batch_stats == 0 (running statistics): dY = gamma * invstd * G and
+ * dgamma / dbeta may be NULL. */
+int g4d_bn_act_grad_f32(long long rows, int c, const float *dOut, int ldg, const float *Y, int ldy, const float *mean, const float *var, float eps,
+                        const float *gamma, const float *beta, int relu, int batch_stats, const float *dgamma, const float *dbeta, float *dY,
+                        int lddy, g4d_stream_t stream);
+/* Adjoint of g4d_pool_rows_f32(is_max = 1): X (groups*S, ldx), dPooled (groups, ldp) read at col0, dX (groups*S, C) dense.  Per (group,
+ * channel) the FIRST row attaining the maximum receives dPooled, the other S - 1 rows 0.  Any S >= 1. */
+int g4d_pool_rows_max_grad_f32(int groups, int s, int c, const float *X, int ldx, const float *dPooled, int ldp, int col0, float *dX,
+                               g4d_stream_t stream);
 
 /* point-major row gather: out[b,j,:] = in[b,idx[b,j],:], rows of c floats (new_xyz = xyz[fps idx] with c=3;
  * same result as gather_points on the transposed tensor, pointnet2_modules.py:32-35, without the two transposes). */
