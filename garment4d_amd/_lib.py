@@ -272,6 +272,11 @@ def call(name, *args):
     return rc
 
 
+def host_array(ctype, values):
+    """`values` as a host array of `ctype`, in the form the C ABI takes it: a void pointer -- which keeps the array alive as long as it lives itself."""
+    return ctypes.cast((ctype * len(values))(*values), ctypes.c_void_p)
+
+
 def ver(t):
     """A tensor's version counter for cache keys, or None for an inference tensor (torch.inference_mode(): no counter is kept -- and no in-place
     update outside inference mode is possible either)."""

@@ -1,10 +1,10 @@
-// Library-level entry points of libg4d_hip: version + thread-local error text.
+// Library-level entry points of libg4d_hip: version + thread-local error text, tuning switches, and the C doors of the whole-stack MLP launchers.
 #include <stdarg.h>
 #include <stddef.h>
 #include <stdlib.h>
 #include <string.h>
 
-#include "g4d_common.h"
+#include "mlp_common.h"
 
 namespace g4d {
 static thread_local char g_err[512] = "";
@@ -183,11 +183,46 @@ extern "C" int g4d_copy_segments_f32(int nseg, float *const *dst, const float *c
     return g4d::check_launch("g4d_copy_segments_f32");
 }
 
+// ---- the whole-stack launchers behind ONE argument block (include/g4d.h): g4d_mlp_run and the seven positional entry points --------------
+// Both doors end in the same StackCall (mlp_common.h) handed to the family's launcher; nothing below them takes positional arguments.
+namespace g4d {
+static StackCall stack_call(const char *name, const g4d_mlp_args &a) {
+    StackCall c = {};
+    c.name = name; c.mode = a.mode; c.rows = a.rows;
+    LinearArgs &in = c.in;
+    in.K = a.K0; in.out = a.out; in.ldo = a.ldo; in.col0 = a.col0; in.pool = a.pool; in.S = a.S;
+    in.X = a.X; in.ldx = a.ldx;
+    in.xyz = a.xyz; in.new_xyz = a.new_xyz; in.feats = a.feats; in.idx = a.idx; in.N = a.N; in.P = a.P; in.C = a.C; in.use_xyz = a.use_xyz;
+    in.known_feats = a.known_feats; in.skip = a.skip; in.dist2 = a.dist2; in.nn_idx = a.nn_idx; in.C2 = a.C2; in.C1 = a.C1; in.m = a.m; in.n = a.n;
+    in.rowptr = a.rowptr; in.colidx = a.colidx; in.vals = a.vals; in.Vg = a.Vg;
+    c.nlayers = a.nlayers; c.W = a.W; c.scale = a.scale; c.shift = a.shift; c.Kpad = a.Kpad; c.Cout = a.Cout; c.relu = a.relu;
+    c.tap_layer = a.tap_layer; c.tap_out = a.tap_out; c.tap_ld = a.tap_ld; c.unknown_grid = a.unknown_grid;
+    return c;
+}
 
-// ---- g4d_mlp_run: the whole-stack launchers behind ONE argument block (include/g4d.h) ----------------------------------------------------
+int stack_call_check(const StackCall &c, const StackRules &r) {
+    const int S = c.in.S, pool = c.in.pool;
+    G4D_REQUIRE(c.mode >= 0 && c.mode <= (r.csr ? LOAD_CSR : LOAD_INTERP), "%s: %s", c.name, r.bad_mode);
+    if (r.max_layers) G4D_REQUIRE(c.nlayers >= 1 && c.nlayers <= r.max_layers, "%s: 1..%d layers", c.name, r.max_layers);
+    G4D_REQUIRE(c.rows >= 0 && c.rows < r.max_rows && c.in.K > 0, "%s: bad sizes", c.name);
+    if (c.rows == 0) return kEmptyLaunch;
+    G4D_REQUIRE(has_layer_arrays(c), "%s: null pointer", c.name);
+    if (!r.max_layers) G4D_REQUIRE(g4d_mlp_chain_supported(c.nlayers, c.Cout), "%s: unsupported layer widths (see g4d_mlp_chain_supported)", c.name);
+    G4D_REQUIRE(pool >= 0 && pool <= 2, "%s: pool must be 0|1|2", c.name);
+    if (pool) G4D_REQUIRE((S == 4 || S == 8 || S == 16 || S == 32 || S == 64) && c.rows % S == 0, "%s: pooling needs S in {4,8,16,32,64}", c.name);
+    for (int l = 0; l < c.nlayers; ++l) {
+        const void *const *Wl = c.W + (size_t)l * r.w_pieces;   // w_pieces consecutive pointers per layer: hi[, mid, lo]
+        G4D_REQUIRE(Wl[0] && (r.w_pieces == 1 || (Wl[1] && Wl[2])) && c.scale[l] && c.shift[l] && c.Kpad[l] % r.kpad_multiple == 0 && c.Cout[l] > 0, "%s: bad layer %d", c.name, l);
+    }
+    G4D_REQUIRE(tap_layer_of(c) < c.nlayers - 1, "%s: tap must be a hidden layer", c.name);
+    return G4D_OK;
+}
+}  // namespace g4d
+
 extern "C" unsigned g4d_mlp_args_size(void) { return (unsigned)sizeof(g4d_mlp_args); }
 
 extern "C" int g4d_mlp_run(int family, const g4d_mlp_args *args, g4d_stream_t stream) {
+    using namespace g4d;
     G4D_REQUIRE(args, "g4d_mlp_run: null argument block");
     G4D_REQUIRE(args->version == G4D_MLP_ARGS_VERSION, "g4d_mlp_run: argument block version %u, this library speaks %d", args->version, G4D_MLP_ARGS_VERSION);
     G4D_REQUIRE(args->size >= 16 && args->size <= sizeof(g4d_mlp_args), "g4d_mlp_run: argument block of %u bytes, this library's is %u (a newer caller?)",
@@ -195,40 +230,87 @@ extern "C" int g4d_mlp_run(int family, const g4d_mlp_args *args, g4d_stream_t st
     g4d_mlp_args a;
     memset(&a, 0, sizeof(a));
     memcpy(&a, args, args->size);                 // an older caller's shorter block: the appended fields read as zero
-    if (args->size < sizeof(g4d_mlp_args)) a.tap_layer = args->size > offsetof(g4d_mlp_args, tap_layer) ? a.tap_layer : -1;
-    typedef const float *const *FPP;
-    typedef const unsigned short *const *HPP;
+    if (args->size < offsetof(g4d_mlp_args, tap_layer) + sizeof(int)) a.tap_layer = -1;   // ... but a tap layer it does not hold WHOLE reads as "none"
+    if (family != G4D_MLP_CHAIN_BF16) a.unknown_grid = nullptr;   // (the one family whose positional forms take it)
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     switch (family) {
-        case G4D_MLP_STACK_F32:
-            return g4d_mlp_stack_f32(a.mode, a.rows, a.K0, a.X, a.ldx, a.N, a.P, a.S, a.C, a.use_xyz, a.xyz, a.new_xyz, a.feats, a.idx, a.n, a.m, a.C2, a.C1,
-                                     a.known_feats, a.skip, a.dist2, a.nn_idx, a.Vg, a.rowptr, a.colidx, a.vals, a.nlayers, reinterpret_cast<FPP>(a.W), a.scale,
-                                     a.shift, a.Kpad, a.Cout, a.relu, a.pool, a.out, a.ldo, a.col0, a.tap_layer, a.tap_out, a.tap_ld, stream);
-        case G4D_MLP_STACK_BF16:
-            return g4d_mlp_stack_bf16(a.mode, a.rows, a.K0, a.X, a.ldx, a.N, a.P, a.S, a.C, a.use_xyz, a.xyz, a.new_xyz, a.feats, a.idx, a.n, a.m, a.C2, a.C1,
-                                      a.known_feats, a.skip, a.dist2, a.nn_idx, a.Vg, a.rowptr, a.colidx, a.vals, a.nlayers, reinterpret_cast<HPP>(a.W), a.scale,
-                                      a.shift, a.Kpad, a.Cout, a.relu, a.pool, a.out, a.ldo, a.col0, a.tap_layer, a.tap_out, a.tap_ld, stream);
-        case G4D_MLP_WAVE_F32:
-            G4D_REQUIRE(!a.tap_out, "g4d_mlp_run(G4D_MLP_WAVE_F32): the wave-autonomous kernel has no tap");
-            return g4d_mlp_wave_f32(a.mode, a.rows, a.K0, a.X, a.ldx, a.N, a.P, a.S, a.C, a.use_xyz, a.xyz, a.new_xyz, a.feats, a.idx, a.n, a.m, a.C2, a.C1,
-                                    a.known_feats, a.skip, a.dist2, a.nn_idx, a.Vg, a.rowptr, a.colidx, a.vals, a.nlayers, reinterpret_cast<FPP>(a.W), a.scale,
-                                    a.shift, a.Kpad, a.Cout, a.relu, a.pool, a.out, a.ldo, a.col0, stream);
-        case G4D_MLP_CHAIN_F32:
-            return g4d_mlp_chain_f32(a.mode, a.rows, a.K0, a.X, a.ldx, a.N, a.P, a.S, a.C, a.use_xyz, a.xyz, a.new_xyz, a.feats, a.idx, a.n, a.m, a.C2, a.C1,
-                                     a.known_feats, a.skip, a.dist2, a.nn_idx, a.nlayers, reinterpret_cast<FPP>(a.W), a.scale, a.shift, a.Kpad, a.Cout, a.relu,
-                                     a.pool, a.out, a.ldo, a.col0, a.tap_layer, a.tap_out, a.tap_ld, stream);
-        case G4D_MLP_CHAIN_BF16:
-            if (a.unknown_grid)
-                return g4d_mlp_chain_cells_bf16(a.mode, a.rows, a.K0, a.X, a.ldx, a.N, a.P, a.S, a.C, a.use_xyz, a.xyz, a.new_xyz, a.feats, a.idx, a.n, a.m, a.C2,
-                                                a.C1, a.known_feats, a.skip, a.dist2, a.nn_idx, a.nlayers, reinterpret_cast<HPP>(a.W), a.scale, a.shift, a.Kpad,
-                                                a.Cout, a.relu, a.pool, a.out, a.ldo, a.col0, a.tap_layer, a.tap_out, a.tap_ld, a.unknown_grid, stream);
-            return g4d_mlp_chain_bf16(a.mode, a.rows, a.K0, a.X, a.ldx, a.N, a.P, a.S, a.C, a.use_xyz, a.xyz, a.new_xyz, a.feats, a.idx, a.n, a.m, a.C2, a.C1,
-                                      a.known_feats, a.skip, a.dist2, a.nn_idx, a.nlayers, reinterpret_cast<HPP>(a.W), a.scale, a.shift, a.Kpad, a.Cout, a.relu,
-                                      a.pool, a.out, a.ldo, a.col0, a.tap_layer, a.tap_out, a.tap_ld, stream);
-        case G4D_MLP_CHAIN_BF16X3:
-            return g4d_mlp_chain_bf16x3(a.mode, a.rows, a.K0, a.X, a.ldx, a.N, a.P, a.S, a.C, a.use_xyz, a.xyz, a.new_xyz, a.feats, a.idx, a.n, a.m, a.C2, a.C1,
-                                        a.known_feats, a.skip, a.dist2, a.nn_idx, a.nlayers, reinterpret_cast<HPP>(a.W), a.scale, a.shift, a.Kpad, a.Cout, a.relu,
-                                        a.pool, a.out, a.ldo, a.col0, a.tap_layer, a.tap_out, a.tap_ld, stream);
+        case G4D_MLP_STACK_F32: return mlp_stack_f32_run(stack_call("g4d_mlp_stack_f32", a), st);
+        case G4D_MLP_STACK_BF16: return mlp_stack_bf16_run(stack_call("g4d_mlp_stack_bf16", a), st);
+        case G4D_MLP_WAVE_F32: return mlp_wave_f32_run(stack_call("g4d_mlp_wave_f32", a), st);
+        case G4D_MLP_CHAIN_F32: return mlp_chain_f32_run(stack_call("g4d_mlp_chain_f32", a), st);
+        case G4D_MLP_CHAIN_BF16: return mlp_chain_bf16_run(stack_call("g4d_mlp_chain_bf16", a), st);   // (with a.unknown_grid: g4d_mlp_chain_cells_bf16)
+        case G4D_MLP_CHAIN_BF16X3: return mlp_chain_bf16x3_run(stack_call("g4d_mlp_chain_bf16x3", a), st);
     }
-    g4d::set_error("g4d_mlp_run: unknown kernel family %d", family);
+    set_error("g4d_mlp_run: unknown kernel family %d", family);
     return G4D_EINVAL;
+}
+
+// The positional entry points: the arguments go into a g4d_mlp_args and through g4d_mlp_run.  The 33 arguments all seven share are spelled
+// ONCE, here (parameters, and the names in the same order for pack_args); each entry point adds its own (CSR loader, grid) by field name.
+#define G4D_MLP_LOADERS                                                                                                                       \
+    int mode, long long rows, int K0, /* DIRECT / CSR */ const float *X, int ldx,                                                            \
+    /* GROUP  */ int N, int P, int S, int C, int use_xyz, const float *xyz, const float *new_xyz, const float *feats, const int *idx,        \
+    /* INTERP */ int n, int m, int C2, int C1, const float *known_feats, const float *skip, const float *dist2, const int *nn_idx
+#define G4D_MLP_LAYERS(WT)                                                                                                                    \
+    int nlayers, const WT *const *W, const float *const *scale, const float *const *shift, const int *Kpad, const int *Cout, const int *relu, \
+    /* output */ int pool, float *out, int ldo, int col0
+#define G4D_MLP_COMMON                                                                                                                        \
+    mode, rows, K0, X, ldx, N, P, S, C, use_xyz, xyz, new_xyz, feats, idx, n, m, C2, C1, known_feats, skip, dist2, nn_idx, nlayers,         \
+    reinterpret_cast<const void *const *>(W), scale, shift, Kpad, Cout, relu, pool, out, ldo, col0
+
+static g4d_mlp_args pack_args(G4D_MLP_LOADERS, G4D_MLP_LAYERS(void), int tap_layer = -1, float *tap_out = nullptr, int tap_ld = 0) {
+    g4d_mlp_args a;
+    memset(&a, 0, sizeof(a));
+    a.size = (unsigned)sizeof(a); a.version = G4D_MLP_ARGS_VERSION;
+    a.mode = mode; a.rows = rows; a.K0 = K0; a.X = X; a.ldx = ldx;
+    a.N = N; a.P = P; a.S = S; a.C = C; a.use_xyz = use_xyz; a.xyz = xyz; a.new_xyz = new_xyz; a.feats = feats; a.idx = idx;
+    a.n = n; a.m = m; a.C2 = C2; a.C1 = C1; a.known_feats = known_feats; a.skip = skip; a.dist2 = dist2; a.nn_idx = nn_idx;
+    a.nlayers = nlayers; a.W = W; a.scale = scale; a.shift = shift; a.Kpad = Kpad; a.Cout = Cout; a.relu = relu;
+    a.pool = pool; a.out = out; a.ldo = ldo; a.col0 = col0; a.tap_layer = tap_layer; a.tap_out = tap_out; a.tap_ld = tap_ld;
+    return a;
+}
+
+// One C entry point for all loaders: `mode` 0 DIRECT, 1 GROUP, 2 INTERP, 3 CSR; loader pointers that a mode does
+// not use are ignored.  Layer descriptors arrive as parallel arrays (host memory) of length nlayers <= 4.
+extern "C" int g4d_mlp_stack_f32(G4D_MLP_LOADERS, /* CSR */ int Vg, const int *rowptr, const int *colidx, const float *vals, G4D_MLP_LAYERS(float),
+                                 int tap_layer, float *tap_out, int tap_ld, g4d_stream_t stream) {
+    g4d_mlp_args a = pack_args(G4D_MLP_COMMON, tap_layer, tap_out, tap_ld);
+    a.Vg = Vg; a.rowptr = rowptr; a.colidx = colidx; a.vals = vals;
+    return g4d_mlp_run(G4D_MLP_STACK_F32, &a, stream);
+}
+
+extern "C" int g4d_mlp_stack_bf16(G4D_MLP_LOADERS, /* CSR */ int Vg, const int *rowptr, const int *colidx, const float *vals, G4D_MLP_LAYERS(unsigned short),
+                                  int tap_layer, float *tap_out, int tap_ld, g4d_stream_t stream) {
+    g4d_mlp_args a = pack_args(G4D_MLP_COMMON, tap_layer, tap_out, tap_ld);
+    a.Vg = Vg; a.rowptr = rowptr; a.colidx = colidx; a.vals = vals;
+    return g4d_mlp_run(G4D_MLP_STACK_BF16, &a, stream);
+}
+
+extern "C" int g4d_mlp_wave_f32(G4D_MLP_LOADERS, /* CSR */ int Vg, const int *rowptr, const int *colidx, const float *vals, G4D_MLP_LAYERS(float),
+                                g4d_stream_t stream) {
+    g4d_mlp_args a = pack_args(G4D_MLP_COMMON);
+    a.Vg = Vg; a.rowptr = rowptr; a.colidx = colidx; a.vals = vals;
+    return g4d_mlp_run(G4D_MLP_WAVE_F32, &a, stream);
+}
+
+extern "C" int g4d_mlp_chain_f32(G4D_MLP_LOADERS, G4D_MLP_LAYERS(float), int tap_layer, float *tap_out, int tap_ld, g4d_stream_t stream) {
+    g4d_mlp_args a = pack_args(G4D_MLP_COMMON, tap_layer, tap_out, tap_ld);
+    return g4d_mlp_run(G4D_MLP_CHAIN_F32, &a, stream);
+}
+
+extern "C" int g4d_mlp_chain_bf16(G4D_MLP_LOADERS, G4D_MLP_LAYERS(unsigned short), int tap_layer, float *tap_out, int tap_ld, g4d_stream_t stream) {
+    g4d_mlp_args a = pack_args(G4D_MLP_COMMON, tap_layer, tap_out, tap_ld);
+    return g4d_mlp_run(G4D_MLP_CHAIN_BF16, &a, stream);
+}
+
+extern "C" int g4d_mlp_chain_cells_bf16(G4D_MLP_LOADERS, G4D_MLP_LAYERS(unsigned short), int tap_layer, float *tap_out, int tap_ld, const void *unknown_grid,
+                                        g4d_stream_t stream) {
+    g4d_mlp_args a = pack_args(G4D_MLP_COMMON, tap_layer, tap_out, tap_ld);
+    a.unknown_grid = unknown_grid;
+    return g4d_mlp_run(G4D_MLP_CHAIN_BF16, &a, stream);
+}
+
+extern "C" int g4d_mlp_chain_bf16x3(G4D_MLP_LOADERS, G4D_MLP_LAYERS(unsigned short), int tap_layer, float *tap_out, int tap_ld, g4d_stream_t stream) {
+    g4d_mlp_args a = pack_args(G4D_MLP_COMMON, tap_layer, tap_out, tap_ld);
+    return g4d_mlp_run(G4D_MLP_CHAIN_BF16X3, &a, stream);
 }

@@ -232,26 +232,26 @@ __global__ void __launch_bounds__(256) fp_head_bf16_kernel(const FpHeadHArgs a) 
 using namespace g4d;
 
 // Takes the launch if it is the instantiated stack and large enough; returns -1 when it is not (the caller then runs the register-chain kernel).
-int g4d::fp_head_bf16_try(long long rows, int n, int m, int C2, int C1, const float *known_feats, const float *dist2, const int *nn_idx, int nlayers,
-                          const unsigned short *const *W, const float *const *scale, const float *const *shift, const int *Kpad, const int *Cout,
-                          const int *relu, int pool, float *out, int ldo, int col0, int tap_layer, float *tap_out, int tap_ld, hipStream_t st,
-                          const void *perm_rec, size_t perm_stride) {
+int g4d::fp_head_bf16_try(const StackCall &c, hipStream_t st) {
+    const LinearArgs &in = c.in;
+    const unsigned short *const *W = reinterpret_cast<const unsigned short *const *>(c.W);
     const int on = (int)tuning("fp_head_bf16_persistent", 1);
     const long long min_rows = tuning("fp_head_bf16_min_rows", 262144);
-    if (!on || rows < min_rows || rows >= (1ll << 31) - 64 || C2 != D0 || C1 != 0 || nlayers != 4 || pool != 0 || col0 != 0) return -1;
-    if (Cout[0] != D1 || Cout[1] != D2 || Cout[2] != D3 || Cout[3] > D4 || Cout[3] < 1 || Kpad[0] != D0 || Kpad[1] != D1 || Kpad[2] != D2 || Kpad[3] != D3) return -1;
-    if (tap_out && (tap_layer != 1 || tap_ld % 4 != 0 || (reinterpret_cast<size_t>(tap_out) & 15) != 0)) return -1;
-    if (n < 16 || m <= 0 || rows % n != 0 || (rows / n) * (long long)m * D0 >= (1ll << 32) || (reinterpret_cast<size_t>(known_feats) & 15) != 0) return -1;
-    G4D_REQUIRE(known_feats && dist2 && nn_idx && out && W[0] && W[1] && W[2] && W[3] && scale[0] && scale[1] && scale[2] && scale[3] && shift[0] && shift[1] && shift[2] && shift[3],
+    if (!on || c.rows < min_rows || c.rows >= (1ll << 31) - 64 || in.C2 != D0 || in.C1 != 0 || c.nlayers != 4 || in.pool != 0 || in.col0 != 0) return -1;
+    if (c.Cout[0] != D1 || c.Cout[1] != D2 || c.Cout[2] != D3 || c.Cout[3] > D4 || c.Cout[3] < 1 || c.Kpad[0] != D0 || c.Kpad[1] != D1 || c.Kpad[2] != D2 || c.Kpad[3] != D3) return -1;
+    if (c.tap_out && (c.tap_layer != 1 || c.tap_ld % 4 != 0 || (reinterpret_cast<size_t>(c.tap_out) & 15) != 0)) return -1;
+    if (in.n < 16 || in.m <= 0 || c.rows % in.n != 0 || (c.rows / in.n) * (long long)in.m * D0 >= (1ll << 32) || (reinterpret_cast<size_t>(in.known_feats) & 15) != 0) return -1;
+    G4D_REQUIRE(in.known_feats && in.dist2 && in.nn_idx && in.out && W[0] && W[1] && W[2] && W[3] && c.scale[0] && c.scale[1] && c.scale[2] && c.scale[3] && c.shift[0] && c.shift[1] && c.shift[2] && c.shift[3],
                 "g4d_mlp_chain_bf16: null pointer");
-    G4D_REQUIRE(ldo >= Cout[3] && (!tap_out || tap_ld >= Cout[1]), "g4d_mlp_chain_bf16: output row stride %d < %d channels or tap stride %d < %d", ldo, Cout[3], tap_ld, Cout[1]);
+    G4D_REQUIRE(in.ldo >= c.Cout[3] && (!c.tap_out || c.tap_ld >= c.Cout[1]), "g4d_mlp_chain_bf16: output row stride %d < %d channels or tap stride %d < %d", in.ldo, c.Cout[3], c.tap_ld, c.Cout[1]);
     FpHeadHArgs a;
-    a.rows = (int)rows; a.n = n; a.m = m; a.feats = known_feats; a.dist2 = dist2; a.nn_idx = nn_idx;
+    a.rows = (int)c.rows; a.n = in.n; a.m = in.m; a.feats = in.known_feats; a.dist2 = in.dist2; a.nn_idx = in.nn_idx;
     a.W1 = W[0]; a.W2 = W[1]; a.W3 = W[2]; a.W4 = W[3];
-    a.sc1 = scale[0]; a.sh1 = shift[0]; a.sc2 = scale[1]; a.sh2 = shift[1]; a.sc3 = scale[2]; a.sh3 = shift[2]; a.sc4 = scale[3]; a.sh4 = shift[3];
-    a.relu1 = relu[0]; a.relu2 = relu[1]; a.relu3 = relu[2]; a.relu4 = relu[3]; a.cout4 = Cout[3];
-    a.out = out; a.ldo = ldo; a.tap = tap_out; a.tap_ld = tap_ld;
-    a.perm_rec = reinterpret_cast<const unsigned char *>(perm_rec); a.perm_stride = perm_stride;
+    a.sc1 = c.scale[0]; a.sh1 = c.shift[0]; a.sc2 = c.scale[1]; a.sh2 = c.shift[1]; a.sc3 = c.scale[2]; a.sh3 = c.shift[2]; a.sc4 = c.scale[3]; a.sh4 = c.shift[3];
+    a.relu1 = c.relu[0]; a.relu2 = c.relu[1]; a.relu3 = c.relu[2]; a.relu4 = c.relu[3]; a.cout4 = c.Cout[3];
+    a.out = in.out; a.ldo = in.ldo; a.tap = c.tap_out; a.tap_ld = c.tap_ld;
+    a.perm_rec = cell_records(c, &a.perm_stride);
+    const unsigned char *perm_rec = a.perm_rec;
     typedef void (*Kern)(const FpHeadHArgs);
     const Kern kern = perm_rec ? fp_head_bf16_kernel<true> : fp_head_bf16_kernel<false>;
     static int resident[2] = {0, 0};
@@ -262,7 +262,7 @@ int g4d::fp_head_bf16_try(long long rows, int n, int m, int C2, int C1, const fl
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 256, 0) != hipSuccess || per_cu < 1) per_cu = 1;
         res = (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess || prop.multiProcessorCount < 1) ? per_cu * 256 : per_cu * prop.multiProcessorCount;
     }
-    const long long want = ((rows + 15) / 16 + 3) / 4;
+    const long long want = ((c.rows + 15) / 16 + 3) / 4;
     hipLaunchKernelGGL(kern, dim3((unsigned)(want < res ? want : res)), dim3(256), 0, st, a);
     return check_launch("g4d_fp_head_bf16");
 }

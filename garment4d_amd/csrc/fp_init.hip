@@ -349,25 +349,25 @@ extern "C" int g4d_fpinit_debug_read(long long *host_out, int clear) {
 using namespace g4d;
 
 // Takes the launch if it is the instantiated stack (skip 96 -> 256 -> 128 -> 128) and large enough; -1 when it is not.
-int g4d::fp_init_try(long long rows, int n, int m, int C1_, const float *skip, const float *table, int tab_ld, const float *dist2, const int *nn_idx,
-                     int nlayers, const float *const *W, const float *const *scale, const float *const *shift, const int *Kpad, const int *Cout,
-                     const int *relu, float *out, int ldo, int col0, int tap_layer, float *tap_out, int tap_ld, hipStream_t st) {
+int g4d::fp_init_try(const StackCall &c, hipStream_t st) {
+    const LinearArgs &in = c.in;   // (in.tab: the table)
+    const float *const *W = reinterpret_cast<const float *const *>(c.W);
     const int on = (int)tuning("fp_init_persistent", 1);
     const long long min_rows = tuning("fp_init_min_rows", 131072);
-    if (!on || rows < min_rows || rows >= (1ll << 31) - 64 || C1_ != C0 || nlayers != 3 || col0 != 0) return -1;
-    if (Cout[0] != C1 || Cout[1] != C2 || Cout[2] != C3 || Kpad[0] != C0 || Kpad[1] != C1 || Kpad[2] != C2) return -1;
-    if (tap_out && (tap_layer != 1 || tap_ld % 4 != 0 || (reinterpret_cast<size_t>(tap_out) & 15) != 0)) return -1;
-    if (n < 16 || m <= 0 || rows % n != 0 || (rows / n) * (long long)m * tab_ld >= (1ll << 32) || tab_ld < C1 || (reinterpret_cast<size_t>(table) & 15) != 0) return -1;
-    G4D_REQUIRE(skip && table && dist2 && nn_idx && out && W[0] && W[1] && W[2] && scale[0] && scale[1] && scale[2] && shift[0] && shift[1] && shift[2],
+    if (!on || c.rows < min_rows || c.rows >= (1ll << 31) - 64 || in.C1 != C0 || c.nlayers != 3 || in.col0 != 0) return -1;
+    if (c.Cout[0] != C1 || c.Cout[1] != C2 || c.Cout[2] != C3 || c.Kpad[0] != C0 || c.Kpad[1] != C1 || c.Kpad[2] != C2) return -1;
+    if (c.tap_out && (c.tap_layer != 1 || c.tap_ld % 4 != 0 || (reinterpret_cast<size_t>(c.tap_out) & 15) != 0)) return -1;
+    if (in.n < 16 || in.m <= 0 || c.rows % in.n != 0 || (c.rows / in.n) * (long long)in.m * in.tab_ld >= (1ll << 32) || in.tab_ld < C1 || (reinterpret_cast<size_t>(in.tab) & 15) != 0) return -1;
+    G4D_REQUIRE(in.skip && in.tab && in.dist2 && in.nn_idx && in.out && W[0] && W[1] && W[2] && c.scale[0] && c.scale[1] && c.scale[2] && c.shift[0] && c.shift[1] && c.shift[2],
                 "g4d_mlp_chain_interp_init_f32: null pointer");
-    if (ldo % 4 != 0 || (reinterpret_cast<size_t>(out) & 15) != 0) return -1;   // (the last layer leaves through 16-byte stores)
-    G4D_REQUIRE(ldo >= Cout[2] && (!tap_out || tap_ld >= Cout[1]) && tab_ld % 4 == 0, "g4d_mlp_chain_interp_init_f32: output row stride %d < %d channels, tap stride %d < %d or table stride %d not a multiple of 4",
-                ldo, Cout[2], tap_ld, Cout[1], tab_ld);
+    if (in.ldo % 4 != 0 || (reinterpret_cast<size_t>(in.out) & 15) != 0) return -1;   // (the last layer leaves through 16-byte stores)
+    G4D_REQUIRE(in.ldo >= c.Cout[2] && (!c.tap_out || c.tap_ld >= c.Cout[1]) && in.tab_ld % 4 == 0, "g4d_mlp_chain_interp_init_f32: output row stride %d < %d channels, tap stride %d < %d or table stride %d not a multiple of 4",
+                in.ldo, c.Cout[2], c.tap_ld, c.Cout[1], in.tab_ld);
     FpInitArgs a;
-    a.rows = (int)rows; a.n = n; a.m = m; a.skip = skip; a.tab = table; a.tab_ld = tab_ld; a.dist2 = dist2; a.nn_idx = nn_idx;
-    a.W1 = W[0]; a.sc1 = scale[0]; a.sh1 = shift[0]; a.W2 = W[1]; a.sc2 = scale[1]; a.sh2 = shift[1]; a.W3 = W[2]; a.sc3 = scale[2]; a.sh3 = shift[2];
-    a.relu1 = relu[0]; a.relu2 = relu[1]; a.relu3 = relu[2];
-    a.out = out; a.ldo = ldo; a.tap = tap_out; a.tap_ld = tap_ld;
+    a.rows = (int)c.rows; a.n = in.n; a.m = in.m; a.skip = in.skip; a.tab = in.tab; a.tab_ld = in.tab_ld; a.dist2 = in.dist2; a.nn_idx = in.nn_idx;
+    a.W1 = W[0]; a.sc1 = c.scale[0]; a.sh1 = c.shift[0]; a.W2 = W[1]; a.sc2 = c.scale[1]; a.sh2 = c.shift[1]; a.W3 = W[2]; a.sc3 = c.scale[2]; a.sh3 = c.shift[2];
+    a.relu1 = c.relu[0]; a.relu2 = c.relu[1]; a.relu3 = c.relu[2];
+    a.out = in.out; a.ldo = in.ldo; a.tap = c.tap_out; a.tap_ld = c.tap_ld;
     static unsigned long long attr = 0;
     if (const int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(fp_init_kernel), kStageBytes, attr, "g4d_fp_init")) return rc;
     static const int resident = [] {
@@ -377,7 +377,7 @@ int g4d::fp_init_try(long long rows, int n, int m, int C1_, const float *skip, c
         if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess || prop.multiProcessorCount < 1) return per_cu * 256;
         return per_cu * prop.multiProcessorCount;
     }();
-    const long long want = ((rows + 15) / 16 + 3) / 4;
+    const long long want = ((c.rows + 15) / 16 + 3) / 4;
     hipLaunchKernelGGL(fp_init_kernel, dim3((unsigned)(want < resident ? want : resident)), dim3(256), kStageBytes, st, a);
     return check_launch("g4d_fp_init");
 }

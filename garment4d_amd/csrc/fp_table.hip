@@ -208,30 +208,32 @@ using namespace g4d;
 
 // Takes the launch if it is the instantiated stack (128-wide table -> 64 -> 32 -> <= 16, ReLU on the first three) and large enough to
 // pipeline; returns -1 when it is not (the caller then runs the register-chain kernel), else the launch status.
-int g4d::fp_table_try(long long rows, int n, int m, int C2, const float *table, const float *dist2, const int *nn_idx, const void *perm_rec,
-                      size_t perm_stride, const float *pre_scale, const float *pre_shift, float *in_tap, int nlayers, const float *const *W,
-                      const float *const *scale, const float *const *shift, const int *Kpad, const int *Cout, const int *relu, float *out, int ldo,
-                      int col0, int tap_layer, float *tap_out, int tap_ld, hipStream_t st) {
+int g4d::fp_table_try(const StackCall &c, hipStream_t st) {
+    const LinearArgs &in = c.in;   // (in.known_feats: the table)
+    const float *const *W = reinterpret_cast<const float *const *>(c.W);
+    float *tap_out = c.tap_out;
+    int tap_ld = c.tap_ld;
     const int on = (int)tuning("fp_table_persistent", 1);          // A/B switch
     const long long min_rows = tuning("fp_table_min_rows", 262144);
     // the FP level alone (round 6): one layer behind the table, 128 -> 64, written where the launch's output goes
-    const bool alone = nlayers == 1 && !tap_out && !in_tap && col0 == 0 && Cout[0] == kC2 && Kpad[0] == kC1 && relu[0];
-    if (alone) { tap_out = out; tap_ld = ldo; }
-    if (!on || rows < min_rows || rows >= (1ll << 31) - 64 || C2 != kC1 || (nlayers != 3 && !alone) || in_tap || col0 != 0 || (!alone && tap_layer != 0) || !tap_out) return -1;
-    if (!alone && (Cout[0] != kC2 || Cout[1] != kC3 || Cout[2] > kC4 || Cout[2] < 1 || Kpad[0] != kC1 || Kpad[1] != kC2 || Kpad[2] != kC3 || !relu[0] || !relu[1])) return -1;
-    if (n < 16 || m <= 0 || rows % n != 0 || (rows / n) * (long long)m * kC1 >= (1ll << 32) || tap_ld % 4 != 0 || (reinterpret_cast<size_t>(tap_out) & 15) != 0 ||
-        (reinterpret_cast<size_t>(table) & 15) != 0) return -1;
-    G4D_REQUIRE(table && dist2 && nn_idx && pre_scale && pre_shift && out && W[0] && scale[0] && shift[0] && (alone || (W[1] && W[2] && scale[1] && scale[2] && shift[1] && shift[2])),
+    const bool alone = c.nlayers == 1 && !tap_out && !in.in_tap && in.col0 == 0 && c.Cout[0] == kC2 && c.Kpad[0] == kC1 && c.relu[0];
+    if (alone) { tap_out = in.out; tap_ld = in.ldo; }
+    if (!on || c.rows < min_rows || c.rows >= (1ll << 31) - 64 || in.C2 != kC1 || (c.nlayers != 3 && !alone) || in.in_tap || in.col0 != 0 || (!alone && c.tap_layer != 0) || !tap_out) return -1;
+    if (!alone && (c.Cout[0] != kC2 || c.Cout[1] != kC3 || c.Cout[2] > kC4 || c.Cout[2] < 1 || c.Kpad[0] != kC1 || c.Kpad[1] != kC2 || c.Kpad[2] != kC3 || !c.relu[0] || !c.relu[1])) return -1;
+    if (in.n < 16 || in.m <= 0 || c.rows % in.n != 0 || (c.rows / in.n) * (long long)in.m * kC1 >= (1ll << 32) || tap_ld % 4 != 0 || (reinterpret_cast<size_t>(tap_out) & 15) != 0 ||
+        (reinterpret_cast<size_t>(in.known_feats) & 15) != 0) return -1;
+    G4D_REQUIRE(in.known_feats && in.dist2 && in.nn_idx && in.pre_scale && in.pre_shift && in.out && W[0] && c.scale[0] && c.shift[0] && (alone || (W[1] && W[2] && c.scale[1] && c.scale[2] && c.shift[1] && c.shift[2])),
                 "g4d_mlp_chain_table_f32: null pointer");
-    G4D_REQUIRE((alone || ldo >= Cout[2]) && tap_ld >= Cout[0], "g4d_mlp_chain_table_f32: output row stride %d or tap stride %d too small", ldo, tap_ld);
+    G4D_REQUIRE((alone || in.ldo >= c.Cout[2]) && tap_ld >= c.Cout[0], "g4d_mlp_chain_table_f32: output row stride %d or tap stride %d too small", in.ldo, tap_ld);
     FpTabArgs a;
-    a.rows = (int)rows; a.n = n; a.m = m; a.tab = table; a.dist2 = dist2; a.nn_idx = nn_idx;
-    a.perm_rec = reinterpret_cast<const unsigned char *>(perm_rec); a.perm_stride = perm_stride;
-    a.ps = pre_scale; a.pf = pre_shift;
-    a.W2 = W[0]; a.sc2 = scale[0]; a.sh2 = shift[0];
-    a.W3 = alone ? nullptr : W[1]; a.sc3 = alone ? nullptr : scale[1]; a.sh3 = alone ? nullptr : shift[1];
-    a.W4 = alone ? nullptr : W[2]; a.sc4 = alone ? nullptr : scale[2]; a.sh4 = alone ? nullptr : shift[2];
-    a.cout4 = alone ? 0 : Cout[2]; a.relu4 = alone ? 0 : relu[2]; a.out = out; a.ldo = ldo; a.tap = tap_out; a.tap_ld = tap_ld;
+    a.rows = (int)c.rows; a.n = in.n; a.m = in.m; a.tab = in.known_feats; a.dist2 = in.dist2; a.nn_idx = in.nn_idx;
+    a.perm_rec = cell_records(c, &a.perm_stride);
+    const unsigned char *perm_rec = a.perm_rec;
+    a.ps = in.pre_scale; a.pf = in.pre_shift;
+    a.W2 = W[0]; a.sc2 = c.scale[0]; a.sh2 = c.shift[0];
+    a.W3 = alone ? nullptr : W[1]; a.sc3 = alone ? nullptr : c.scale[1]; a.sh3 = alone ? nullptr : c.shift[1];
+    a.W4 = alone ? nullptr : W[2]; a.sc4 = alone ? nullptr : c.scale[2]; a.sh4 = alone ? nullptr : c.shift[2];
+    a.cout4 = alone ? 0 : c.Cout[2]; a.relu4 = alone ? 0 : c.relu[2]; a.out = in.out; a.ldo = in.ldo; a.tap = tap_out; a.tap_ld = tap_ld;
     // ring depth 2 (measured at 240 clouds, 1.97 M rows: 2 k-steps ahead 422 us, 4: 436-440, 8: 448 -- the deeper rings only add registers)
     typedef void (*Kern)(const FpTabArgs);
     const Kern kern = alone ? (perm_rec ? fp_table_head_kernel<true, 2, false> : fp_table_head_kernel<false, 2, false>)
@@ -244,7 +246,7 @@ int g4d::fp_table_try(long long rows, int n, int m, int C2, const float *table, 
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 256, 0) != hipSuccess || per_cu < 1) per_cu = 1;
         res = (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess || prop.multiProcessorCount < 1) ? per_cu * 256 : per_cu * prop.multiProcessorCount;
     }
-    const long long want = ((rows + 15) / 16 + 3) / 4;
+    const long long want = ((c.rows + 15) / 16 + 3) / 4;
     hipLaunchKernelGGL(kern, dim3((unsigned)(want < res ? want : res)), dim3(256), 0, st, a);
     return check_launch("g4d_fp_table_head");
 }

@@ -650,59 +650,41 @@ extern "C" int g4d_launch_group_abort(void) {
     return G4D_OK;
 }
 
-static int chain_f32_impl(int mode, long long rows, int K0, const float *X, int ldx, int N, int P, int S, int C, int use_xyz,
-                          const float *xyz, const float *new_xyz, const float *feats, const int *idx, int n, int m, int C2,
-                          int C1, const float *known_feats, const float *skip, const float *dist2, const int *nn_idx,
-                          int nlayers, const float *const *W, const float *const *scale, const float *const *shift,
-                          const int *Kpad, const int *Cout, const int *relu, int pool, float *out, int ldo, int col0,
-                          int tap_layer, float *tap_out, int tap_ld, const float *pre_scale, const float *pre_shift, float *in_tap,
-                          int in_tap_ld, const float *tab, int tab_ld, const float *tab_wx, g4d_stream_t stream, const void *perm_grid = nullptr) {
-    G4D_REQUIRE(mode == LOAD_DIRECT || mode == LOAD_GROUP || mode == LOAD_INTERP, "g4d_mlp_chain_f32: mode must be 0 (direct), 1 (group) or 2 (interp)");
-    G4D_REQUIRE(rows >= 0 && rows < (1ll << 31) - 256 && K0 > 0, "g4d_mlp_chain_f32: bad sizes");
-    if (rows == 0) return G4D_OK;
-    G4D_REQUIRE(W && scale && shift && Kpad && Cout && relu && out, "g4d_mlp_chain_f32: null pointer");
-    G4D_REQUIRE(g4d_mlp_chain_supported(nlayers, Cout), "g4d_mlp_chain_f32: unsupported layer widths (see g4d_mlp_chain_supported)");
-    G4D_REQUIRE(pool >= 0 && pool <= 2, "g4d_mlp_chain_f32: pool must be 0|1|2");
-    if (pool) G4D_REQUIRE((S == 4 || S == 8 || S == 16 || S == 32 || S == 64) && rows % S == 0, "g4d_mlp_chain_f32: pooling needs S in {4,8,16,32,64}");
+// The register-chain launch behind g4d_mlp_chain_f32 and the table entry points below (which name it in their error texts too).
+int g4d::mlp_chain_f32_run(const StackCall &c, hipStream_t st) {
+    static const StackRules rules = {"mode must be 0 (direct), 1 (group) or 2 (interp)", false, 0, (1ll << 31) - 256, 16, 1};
+    if (const int rc = stack_call_check(c, rules)) return rc == kEmptyLaunch ? G4D_OK : rc;
+    const LinearArgs &in = c.in;
+    const int mode = c.mode, nlayers = c.nlayers, K0 = in.K, *Kpad = c.Kpad, *Cout = c.Cout;
     static const int xcd_swz = getenv("G4D_CHAIN_XCD") ? atoi(getenv("G4D_CHAIN_XCD")) : 1;          // A/B switch
     ChainArgs s = {};
-    s.in.rows = (int)rows; s.in.K = K0; s.in.out = out; s.in.ldo = ldo; s.in.col0 = col0; s.in.pool = pool; s.in.S = S > 0 ? S : 1;
-    s.in.X = X; s.in.ldx = ldx;
-    s.in.xyz = xyz; s.in.new_xyz = new_xyz; s.in.feats = feats; s.in.idx = idx; s.in.N = N; s.in.P = P; s.in.C = C; s.in.use_xyz = use_xyz;
-    s.in.known_feats = known_feats; s.in.skip = skip; s.in.dist2 = dist2; s.in.nn_idx = nn_idx; s.in.C2 = C2; s.in.C1 = C1; s.in.m = m; s.in.n = n;
-    if (perm_grid) {
-        G4D_REQUIRE(mode == LOAD_INTERP && pool == 0 && n > 0 && rows % n == 0, "g4d_mlp_chain_*_cells_f32: cell-ordered rows need the interpolating loader, no pooling, whole clouds");
-        size_t off = 0, stride = 0;
-        grid_sorted_layout(n, &off, &stride);
-        s.in.perm_rec = reinterpret_cast<const unsigned char *>(perm_grid) + off; s.in.perm_stride = stride;
+    s.in = kernel_in(c);
+    if (c.unknown_grid) {
+        G4D_REQUIRE(mode == LOAD_INTERP && in.pool == 0 && in.n > 0 && c.rows % in.n == 0, "g4d_mlp_chain_*_cells_f32: cell-ordered rows need the interpolating loader, no pooling, whole clouds");
+        s.in.perm_rec = cell_records(c, &s.in.perm_stride);
     }
-    s.tap_layer = tap_out ? tap_layer : -1; s.tap_out = tap_out; s.tap_ld = tap_ld;
-    G4D_REQUIRE(s.tap_layer < nlayers - 1, "g4d_mlp_chain_f32: tap must be a hidden layer");
-    if (tab && mode == LOAD_INTERP) {
-        G4D_REQUIRE(C2 == 0 && C1 > 0 && K0 == C1 && skip && nlayers >= 2 && Cout[0] % 16 == 0 && tab_ld >= Cout[0] && tab_ld % 4 == 0 &&
-                    (reinterpret_cast<size_t>(tab) & 15) == 0 && !pre_scale, "g4d_mlp_chain_interp_init_f32: needs skip features, >= 2 layers, a first-layer width that "
+    s.tap_layer = tap_layer_of(c); s.tap_out = c.tap_out; s.tap_ld = c.tap_ld;
+    // the table loaders (the entry points below set these fields of `in`; they reach the kernel as they stand)
+    if (in.tab && mode == LOAD_INTERP) {
+        G4D_REQUIRE(in.C2 == 0 && in.C1 > 0 && K0 == in.C1 && in.skip && nlayers >= 2 && Cout[0] % 16 == 0 && in.tab_ld >= Cout[0] && in.tab_ld % 4 == 0 &&
+                    (reinterpret_cast<size_t>(in.tab) & 15) == 0 && !in.pre_scale, "g4d_mlp_chain_interp_init_f32: needs skip features, >= 2 layers, a first-layer width that "
                     "is a multiple of 16 and a 16-byte aligned table at least that wide");
-        s.in.tab = tab; s.in.tab_ld = tab_ld;
-    } else if (tab) {
-        G4D_REQUIRE(mode == LOAD_GROUP && K0 % 16 == 0 && tab_ld >= K0 && tab_ld % 4 == 0 && (reinterpret_cast<size_t>(tab) & 15) == 0 && tab_wx && pre_scale &&
-                    pre_shift && xyz && new_xyz && idx, "g4d_mlp_chain_group_table_f32: needs a 16-byte aligned table whose width is a multiple of 16, the xyz "
+    } else if (in.tab) {
+        G4D_REQUIRE(mode == LOAD_GROUP && K0 % 16 == 0 && in.tab_ld >= K0 && in.tab_ld % 4 == 0 && (reinterpret_cast<size_t>(in.tab) & 15) == 0 && in.tab_wx && in.pre_scale &&
+                    in.pre_shift && in.xyz && in.new_xyz && in.idx, "g4d_mlp_chain_group_table_f32: needs a 16-byte aligned table whose width is a multiple of 16, the xyz "
                     "weights, the affine and the grouping inputs");
-        s.in.tab = tab; s.in.tab_ld = tab_ld; s.in.tab_wx = tab_wx; s.in.pre_scale = pre_scale; s.in.pre_shift = pre_shift;
-    } else if (pre_scale) {
-        G4D_REQUIRE(mode == LOAD_INTERP && C1 == 0 && C2 % 16 == 0 && K0 == C2 && pre_shift, "g4d_mlp_chain_table_f32: needs the interpolating loader, "
+    } else if (in.pre_scale) {
+        G4D_REQUIRE(mode == LOAD_INTERP && in.C1 == 0 && in.C2 % 16 == 0 && K0 == in.C2 && in.pre_shift, "g4d_mlp_chain_table_f32: needs the interpolating loader, "
                     "no skip features and a table width that is a multiple of 16");
-        G4D_REQUIRE(!in_tap || (in_tap_ld >= C2 && in_tap_ld % 4 == 0 && (reinterpret_cast<size_t>(in_tap) & 15) == 0), "g4d_mlp_chain_table_f32: bad input tap");
-        s.in.pre_scale = pre_scale; s.in.pre_shift = pre_shift; s.in.in_tap = in_tap; s.in.in_tap_ld = in_tap_ld;
+        G4D_REQUIRE(!in.in_tap || (in.in_tap_ld >= in.C2 && in.in_tap_ld % 4 == 0 && (reinterpret_cast<size_t>(in.in_tap) & 15) == 0), "g4d_mlp_chain_table_f32: bad input tap");
     }
     for (int l = 0; l < nlayers; ++l) {
-        G4D_REQUIRE(W[l] && scale[l] && shift[l] && Kpad[l] % 16 == 0 && Cout[l] > 0, "g4d_mlp_chain_f32: bad layer %d", l);
         G4D_REQUIRE(Kpad[l] >= (l == 0 ? K0 : Cout[l - 1]), "g4d_mlp_chain_f32: Kpad of layer %d too small", l);
-        s.layer[l].W = W[l]; s.layer[l].scale = scale[l]; s.layer[l].shift = shift[l];
-        s.layer[l].kst = Kpad[l] / 16; s.layer[l].relu = relu[l]; s.layer[l].cout = Cout[l];
+        s.layer[l].W = static_cast<const float *>(c.W[l]); s.layer[l].scale = c.scale[l]; s.layer[l].shift = c.shift[l];
+        s.layer[l].kst = Kpad[l] / 16; s.layer[l].relu = c.relu[l]; s.layer[l].cout = Cout[l];
     }
     s.xcd_swz = xcd_swz;
     const int key = chain_key(nlayers, Cout);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     // rows per wave (16 * MT).  Measured on the cfg2 stacks (scripts/time_stacks.py, G4D_CHAIN_MT sweep): 32 rows per wave win
     // once the launch still has >= 2048 waves (each weight fragment load then feeds 8 MFMAs); 16 rows per wave otherwise (small
     // launches need the waves); 64 rows per wave never won.  The widest stacks (128-wide first layer) at 1024 waves -- SA3 scale 1 of
@@ -710,7 +692,7 @@ static int chain_f32_impl(int mode, long long rows, int K0, const float *X, int 
     // registers: one wave per SIMD and none on a CU that hosts a sampling workgroup; with 16 batches in flight the 16-row one (212
     // registers, two per SIMD, one beside the FPS waves) gives 30.2k instead of 29.8k frames/s, so it is the default
     // (G4D_CHAIN_MT2_MIN_WAVES_WIDE=1024 restores the other choice).
-    const long long waves32 = (rows + 31) / 32;
+    const long long waves32 = (c.rows + 31) / 32;
     static const int mt_env = getenv("G4D_CHAIN_MT") ? atoi(getenv("G4D_CHAIN_MT")) : 0;  // tuning hook: 1 | 2
     const bool wide = key >= 8000000;
     static const long long mt2_min = getenv("G4D_CHAIN_MT2_MIN_WAVES") ? atoll(getenv("G4D_CHAIN_MT2_MIN_WAVES")) : 2048;      // tuning hooks
@@ -725,15 +707,11 @@ static int chain_f32_impl(int mode, long long rows, int K0, const float *X, int 
     return chain_launch_one(mode, key, mt, s, st);
 }
 
-extern "C" int g4d_mlp_chain_f32(int mode, long long rows, int K0, const float *X, int ldx, int N, int P, int S, int C, int use_xyz,
-                                 const float *xyz, const float *new_xyz, const float *feats, const int *idx, int n, int m, int C2,
-                                 int C1, const float *known_feats, const float *skip, const float *dist2, const int *nn_idx,
-                                 int nlayers, const float *const *W, const float *const *scale, const float *const *shift,
-                                 const int *Kpad, const int *Cout, const int *relu, int pool, float *out, int ldo, int col0,
-                                 int tap_layer, float *tap_out, int tap_ld, g4d_stream_t stream) {
-    return chain_f32_impl(mode, rows, K0, X, ldx, N, P, S, C, use_xyz, xyz, new_xyz, feats, idx, n, m, C2, C1, known_feats, skip, dist2, nn_idx,
-                          nlayers, W, scale, shift, Kpad, Cout, relu, pool, out, ldo, col0, tap_layer, tap_out, tap_ld, nullptr, nullptr, nullptr,
-                          0, nullptr, 0, nullptr, stream);
+// g4d_mlp_chain_table_f32 and its cell-ordered form (c.unknown_grid) once their call is described; large launches of the last-level stack
+// go to fp_table.hip (bit-identical)
+static int chain_table_run(const StackCall &c, hipStream_t st) {
+    if (const int rc = has_layer_arrays(c) ? fp_table_try(c, st) : -1; rc != -1) return rc;
+    return mlp_chain_f32_run(c, st);
 }
 
 // Feature propagation without skip features, first layer pre-contracted (pointnet2_modules.py:127-156): the conv of the first
@@ -748,14 +726,13 @@ extern "C" int g4d_mlp_chain_table_f32(long long rows, int n, int m, int C2, con
                                        const int *Cout, const int *relu, float *out, int ldo, int col0, int tap_layer, float *tap_out,
                                        int tap_ld, g4d_stream_t stream) {
     G4D_REQUIRE(table && dist2 && nn_idx && pre_scale && pre_shift, "g4d_mlp_chain_table_f32: null pointer");
-    if (W && scale && shift && Kpad && Cout && relu && out) {   // large launches of the last-level stack: fp_table.hip (bit-identical)
-        const int rc = fp_table_try(rows, n, m, C2, table, dist2, nn_idx, nullptr, 0, pre_scale, pre_shift, in_tap, nlayers, W, scale, shift, Kpad, Cout, relu,
-                                    out, ldo, col0, tap_layer, tap_out, tap_ld, reinterpret_cast<hipStream_t>(stream));
-        if (rc != -1) return rc;
-    }
-    return chain_f32_impl(LOAD_INTERP, rows, C2, nullptr, 0, 0, 0, 1, 0, 0, nullptr, nullptr, nullptr, nullptr, n, m, C2, 0, table, nullptr, dist2,
-                          nn_idx, nlayers, W, scale, shift, Kpad, Cout, relu, 0, out, ldo, col0, tap_layer, tap_out, tap_ld, pre_scale, pre_shift,
-                          in_tap, in_tap_ld, nullptr, 0, nullptr, stream);
+    StackCall c = {};
+    c.name = "g4d_mlp_chain_f32"; c.mode = LOAD_INTERP; c.rows = rows;
+    c.in.K = C2; c.in.S = 1; c.in.n = n; c.in.m = m; c.in.C2 = C2; c.in.known_feats = table; c.in.dist2 = dist2; c.in.nn_idx = nn_idx;
+    c.in.pre_scale = pre_scale; c.in.pre_shift = pre_shift; c.in.in_tap = in_tap; c.in.in_tap_ld = in_tap_ld;
+    c.nlayers = nlayers; c.W = reinterpret_cast<const void *const *>(W); c.scale = scale; c.shift = shift; c.Kpad = Kpad; c.Cout = Cout; c.relu = relu;
+    c.in.out = out; c.in.ldo = ldo; c.in.col0 = col0; c.tap_layer = tap_layer; c.tap_out = tap_out; c.tap_ld = tap_ld;
+    return chain_table_run(c, reinterpret_cast<hipStream_t>(stream));
 }
 
 // g4d_mlp_chain_table_f32 over CELL-ORDERED rows: `unknown_grid` is the ball-grid workspace of the unknown cloud (g4d_ball_grid_build_f32 /
@@ -769,17 +746,13 @@ extern "C" int g4d_mlp_chain_table_cells_f32(long long rows, int n, int m, int C
                                              const float *const *shift, const int *Kpad, const int *Cout, const int *relu, float *out, int ldo,
                                              int col0, int tap_layer, float *tap_out, int tap_ld, g4d_stream_t stream) {
     G4D_REQUIRE(table && dist2 && nn_idx && pre_scale && pre_shift && unknown_grid, "g4d_mlp_chain_table_cells_f32: null pointer");
-    if (W && scale && shift && Kpad && Cout && relu && out && n > 0) {   // large launches of the last-level stack: fp_table.hip (bit-identical)
-        size_t off = 0, stride = 0;
-        grid_sorted_layout(n, &off, &stride);
-        const int rc = fp_table_try(rows, n, m, C2, table, dist2, nn_idx, reinterpret_cast<const unsigned char *>(unknown_grid) + off, stride, pre_scale,
-                                    pre_shift, in_tap, nlayers, W, scale, shift, Kpad, Cout, relu, out, ldo, col0, tap_layer, tap_out, tap_ld,
-                                    reinterpret_cast<hipStream_t>(stream));
-        if (rc != -1) return rc;
-    }
-    return chain_f32_impl(LOAD_INTERP, rows, C2, nullptr, 0, 0, 0, 1, 0, 0, nullptr, nullptr, nullptr, nullptr, n, m, C2, 0, table, nullptr, dist2,
-                          nn_idx, nlayers, W, scale, shift, Kpad, Cout, relu, 0, out, ldo, col0, tap_layer, tap_out, tap_ld, pre_scale, pre_shift,
-                          in_tap, in_tap_ld, nullptr, 0, nullptr, stream, unknown_grid);
+    StackCall c = {};
+    c.name = "g4d_mlp_chain_f32"; c.mode = LOAD_INTERP; c.rows = rows;
+    c.in.K = C2; c.in.S = 1; c.in.n = n; c.in.m = m; c.in.C2 = C2; c.in.known_feats = table; c.in.dist2 = dist2; c.in.nn_idx = nn_idx;
+    c.in.pre_scale = pre_scale; c.in.pre_shift = pre_shift; c.in.in_tap = in_tap; c.in.in_tap_ld = in_tap_ld; c.unknown_grid = unknown_grid;
+    c.nlayers = nlayers; c.W = reinterpret_cast<const void *const *>(W); c.scale = scale; c.shift = shift; c.Kpad = Kpad; c.Cout = Cout; c.relu = relu;
+    c.in.out = out; c.in.ldo = ldo; c.in.col0 = col0; c.tap_layer = tap_layer; c.tap_out = tap_out; c.tap_ld = tap_ld;
+    return chain_table_run(c, reinterpret_cast<hipStream_t>(stream));
 }
 
 // Set abstraction with the feature part of its first layer pre-contracted (pointnet2_utils.py:232-265 + the first SharedMLP layer):
@@ -805,17 +778,21 @@ extern "C" int g4d_mlp_chain_group_table_ws_f32(long long rows, int N, int P, in
                                                 const float *const *shift, const int *Kpad, const int *Cout, const int *relu, int pool,
                                                 float *out, int ldo, int col0, void *ws, long long ws_bytes, g4d_stream_t stream) {
     G4D_REQUIRE(table && Kt > 0, "g4d_mlp_chain_group_table_f32: null table");
-    if (xyz && new_xyz && idx && tab_wx && pre_scale && pre_shift && W && scale && shift && Kpad && Cout && relu && out && (tab_ld >= Kt || tab_ld == 0) && tab_ld % 4 == 0 &&
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    StackCall c = {};
+    c.name = "g4d_mlp_chain_f32"; c.mode = LOAD_GROUP; c.rows = rows;
+    c.in.K = Kt; c.in.N = N; c.in.P = P; c.in.S = S; c.in.use_xyz = 1; c.in.xyz = xyz; c.in.new_xyz = new_xyz; c.in.idx = idx;
+    c.in.tab = table; c.in.tab_ld = tab_ld; c.in.tab_wx = tab_wx; c.in.pre_scale = pre_scale; c.in.pre_shift = pre_shift;
+    c.nlayers = nlayers; c.W = reinterpret_cast<const void *const *>(W); c.scale = scale; c.shift = shift; c.Kpad = Kpad; c.Cout = Cout; c.relu = relu;
+    c.in.pool = pool; c.in.out = out; c.in.ldo = ldo; c.in.col0 = col0; c.tap_layer = -1; c.ws = ws; c.ws_bytes = ws_bytes;
+    if (xyz && new_xyz && idx && tab_wx && pre_scale && pre_shift && has_layer_arrays(c) && (tab_ld >= Kt || tab_ld == 0) && tab_ld % 4 == 0 &&
         (reinterpret_cast<size_t>(table) & 15) == 0 && P > 0 && N > 0) {
         // large launches: the persistent, software-pipelined kernel (sa_table.hip; bit-identical results).  Inside a launch group it simply goes out
         // on its own -- merging launches pays only while they are small.
-        const int rc = sa_table_try(rows, N, P, S, xyz, new_xyz, idx, table, tab_ld, Kt, tab_wx, pre_scale, pre_shift, nlayers, W, scale, shift, Kpad,
-                                    Cout, relu, pool, out, ldo, col0, reinterpret_cast<hipStream_t>(stream), ws, ws_bytes);
+        const int rc = sa_table_try(c, st);
         if (rc != -1) return rc;
     }
-    return chain_f32_impl(LOAD_GROUP, rows, Kt, nullptr, 0, N, P, S, 0, 1, xyz, new_xyz, nullptr, idx, 0, 0, 0, 0, nullptr, nullptr, nullptr,
-                          nullptr, nlayers, W, scale, shift, Kpad, Cout, relu, pool, out, ldo, col0, -1, nullptr, 0, pre_scale, pre_shift, nullptr, 0,
-                          table, tab_ld, tab_wx, stream);
+    return mlp_chain_f32_run(c, st);
 }
 
 // Feature propagation WITH skip features, the known-feature part of the first layer pre-contracted (pointnet2_modules.py:127-156):
@@ -829,12 +806,14 @@ extern "C" int g4d_mlp_chain_interp_init_f32(long long rows, int n, int m, int C
                                              const int *relu, float *out, int ldo, int col0, int tap_layer, float *tap_out, int tap_ld,
                                              g4d_stream_t stream) {
     G4D_REQUIRE(table && skip && dist2 && nn_idx, "g4d_mlp_chain_interp_init_f32: null pointer");
-    if (W && scale && shift && Kpad && Cout && relu && out) {   // large launches of the middle FP level's stack: fp_init.hip (bit-identical)
-        const int rc = fp_init_try(rows, n, m, C1, skip, table, tab_ld, dist2, nn_idx, nlayers, W, scale, shift, Kpad, Cout, relu, out, ldo, col0, tap_layer,
-                                   tap_out, tap_ld, reinterpret_cast<hipStream_t>(stream));
-        if (rc != -1) return rc;
-    }
-    return chain_f32_impl(LOAD_INTERP, rows, C1, nullptr, 0, 0, 0, 1, 0, 0, nullptr, nullptr, nullptr, nullptr, n, m, 0, C1, nullptr, skip, dist2,
-                          nn_idx, nlayers, W, scale, shift, Kpad, Cout, relu, 0, out, ldo, col0, tap_layer, tap_out, tap_ld, nullptr, nullptr,
-                          nullptr, 0, table, tab_ld, nullptr, stream);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    StackCall c = {};
+    c.name = "g4d_mlp_chain_f32"; c.mode = LOAD_INTERP; c.rows = rows;
+    c.in.K = C1; c.in.S = 1; c.in.n = n; c.in.m = m; c.in.C1 = C1; c.in.skip = skip; c.in.dist2 = dist2; c.in.nn_idx = nn_idx;
+    c.in.tab = table; c.in.tab_ld = tab_ld;
+    c.nlayers = nlayers; c.W = reinterpret_cast<const void *const *>(W); c.scale = scale; c.shift = shift; c.Kpad = Kpad; c.Cout = Cout; c.relu = relu;
+    c.in.out = out; c.in.ldo = ldo; c.in.col0 = col0; c.tap_layer = tap_layer; c.tap_out = tap_out; c.tap_ld = tap_ld;
+    // large launches of the middle FP level's stack: fp_init.hip (bit-identical)
+    if (const int rc = has_layer_arrays(c) ? fp_init_try(c, st) : -1; rc != -1) return rc;
+    return mlp_chain_f32_run(c, st);
 }

@@ -445,40 +445,26 @@ static void launch_chain_h(int mode, const ChainArgsH &s, hipStream_t st) {
 
 using namespace g4d;
 
-extern "C" int g4d_mlp_chain_supported(int nlayers, const int *Cout);
-
-static int chain_bf16_impl(const char *name, int nspl, int mode, long long rows, int K0, const float *X, int ldx, int N, int P, int S, int C, int use_xyz,
-                           const float *xyz, const float *new_xyz, const float *feats, const int *idx, int n, int m, int C2,
-                           int C1, const float *known_feats, const float *skip, const float *dist2, const int *nn_idx,
-                           int nlayers, const unsigned short *const *W, const float *const *scale, const float *const *shift,
-                           const int *Kpad, const int *Cout, const int *relu, int pool, float *out, int ldo, int col0,
-                           int tap_layer, float *tap_out, int tap_ld, g4d_stream_t stream) {
-    G4D_REQUIRE(mode == LOAD_DIRECT || mode == LOAD_GROUP || mode == LOAD_INTERP, "%s: mode must be 0, 1 or 2", name);
-    G4D_REQUIRE(rows >= 0 && rows < (1ll << 31) - 256 && K0 > 0, "%s: bad sizes", name);
-    if (rows == 0) return G4D_OK;
-    G4D_REQUIRE(W && scale && shift && Kpad && Cout && relu && out, "%s: null pointer", name);
-    G4D_REQUIRE(g4d_mlp_chain_supported(nlayers, Cout), "%s: unsupported layer widths (see g4d_mlp_chain_supported)", name);
-    G4D_REQUIRE(pool >= 0 && pool <= 2, "%s: pool must be 0|1|2", name);
-    if (pool) G4D_REQUIRE((S == 4 || S == 8 || S == 16 || S == 32 || S == 64) && rows % S == 0, "%s: pooling needs S in {4,8,16,32,64}", name);
+// nspl weight pieces per layer: 1 = g4d_mlp_chain_bf16, 3 (hi | mid | lo) = g4d_mlp_chain_bf16x3
+static int chain_bf16_impl(const StackCall &c, int nspl, hipStream_t st) {
+    const char *name = c.name;
+    const StackRules rules = {"mode must be 0, 1 or 2", false, 0, (1ll << 31) - 256, 32, nspl};
+    if (const int rc = stack_call_check(c, rules)) return rc == kEmptyLaunch ? G4D_OK : rc;
+    const int mode = c.mode, nlayers = c.nlayers, K0 = c.in.K, *Kpad = c.Kpad, *Cout = c.Cout;
+    const unsigned short *const *W = reinterpret_cast<const unsigned short *const *>(c.W);
     ChainArgsH s = {};
-    s.in.rows = (int)rows; s.in.K = K0; s.in.out = out; s.in.ldo = ldo; s.in.col0 = col0; s.in.pool = pool; s.in.S = S > 0 ? S : 1;
-    s.in.X = X; s.in.ldx = ldx;
-    s.in.xyz = xyz; s.in.new_xyz = new_xyz; s.in.feats = feats; s.in.idx = idx; s.in.N = N; s.in.P = P; s.in.C = C; s.in.use_xyz = use_xyz;
-    s.in.known_feats = known_feats; s.in.skip = skip; s.in.dist2 = dist2; s.in.nn_idx = nn_idx; s.in.C2 = C2; s.in.C1 = C1; s.in.m = m; s.in.n = n;
-    s.tap_layer = tap_out ? tap_layer : -1; s.tap_out = tap_out; s.tap_ld = tap_ld;
-    G4D_REQUIRE(s.tap_layer < nlayers - 1, "%s: tap must be a hidden layer", name);
+    s.in = kernel_in(c);
+    s.tap_layer = tap_layer_of(c); s.tap_out = c.tap_out; s.tap_ld = c.tap_ld;
     int key = 0;
     for (int l = 0; l < 4; ++l) key = key * 100 + (l < nlayers ? (Cout[l] + 15) / 16 : 0);
     for (int l = 0; l < nlayers; ++l) {
         const unsigned short *const *Wl = W + (size_t)l * nspl;   // nspl consecutive pointers per layer: hi[, mid, lo]
-        G4D_REQUIRE(Wl[0] && (nspl == 1 || (Wl[1] && Wl[2])) && scale[l] && shift[l] && Kpad[l] % 32 == 0 && Cout[l] > 0, "%s: bad layer %d", name, l);
         G4D_REQUIRE(Kpad[l] >= (l == 0 ? K0 : Cout[l - 1]), "%s: Kpad of layer %d too small", name, l);
         s.layer[l].W = Wl[0]; s.layer[l].Wm = nspl == 3 ? Wl[1] : nullptr; s.layer[l].Wl = nspl == 3 ? Wl[2] : nullptr;
-        s.layer[l].scale = scale[l]; s.layer[l].shift = shift[l];
-        s.layer[l].kst = Kpad[l] / 32; s.layer[l].relu = relu[l]; s.layer[l].cout = Cout[l];
+        s.layer[l].scale = c.scale[l]; s.layer[l].shift = c.shift[l];
+        s.layer[l].kst = Kpad[l] / 32; s.layer[l].relu = c.relu[l]; s.layer[l].cout = Cout[l];
     }
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const long long waves32 = (rows + 31) / 32;
+    const long long waves32 = (c.rows + 31) / 32;
     static const int mt_env = getenv("G4D_CHAIN_MT") ? atoi(getenv("G4D_CHAIN_MT")) : 0;
     const bool wide = nspl == 3 && key >= 8000000;   // split mode: three weight pieces per fragment -> reuse them over 32 rows earlier
     const int mt = mt_env ? (mt_env >= 2 ? 2 : 1) : ((waves32 >= 2048 || (wide && waves32 >= 1024)) ? 2 : 1);
@@ -510,49 +496,14 @@ static int chain_bf16_impl(const char *name, int nspl, int mode, long long rows,
     return check_launch(name);
 }
 
-extern "C" int g4d_mlp_chain_bf16(int mode, long long rows, int K0, const float *X, int ldx, int N, int P, int S, int C, int use_xyz,
-                                  const float *xyz, const float *new_xyz, const float *feats, const int *idx, int n, int m, int C2,
-                                  int C1, const float *known_feats, const float *skip, const float *dist2, const int *nn_idx,
-                                  int nlayers, const unsigned short *const *W, const float *const *scale, const float *const *shift,
-                                  const int *Kpad, const int *Cout, const int *relu, int pool, float *out, int ldo, int col0,
-                                  int tap_layer, float *tap_out, int tap_ld, g4d_stream_t stream) {
-    if (mode == LOAD_INTERP && known_feats && dist2 && nn_idx && W && scale && shift && Kpad && Cout && relu && out) {   // large launches of config 3's last level: fp_head_bf16.hip (bit-identical)
-        const int rc = fp_head_bf16_try(rows, n, m, C2, C1, known_feats, dist2, nn_idx, nlayers, W, scale, shift, Kpad, Cout, relu, pool, out, ldo, col0, tap_layer,
-                                        tap_out, tap_ld, reinterpret_cast<hipStream_t>(stream));
-        if (rc != -1) return rc;
-    }
-    if (mode == LOAD_GROUP && W && scale && shift && Kpad && Cout && relu && out) {   // large launches of config 3's SA levels: sa_group_bf16.hip (bit-identical)
-        const int rc = sa_group_bf16_try(rows, N, P, S, C, use_xyz, xyz, new_xyz, feats, idx, nlayers, W, scale, shift, Kpad, Cout, relu, pool, out, ldo, col0,
-                                         tap_out, reinterpret_cast<hipStream_t>(stream));
-        if (rc != -1) return rc;
-    }
-    return chain_bf16_impl("g4d_mlp_chain_bf16", 1, mode, rows, K0, X, ldx, N, P, S, C, use_xyz, xyz, new_xyz, feats, idx, n, m, C2, C1, known_feats, skip,
-                           dist2, nn_idx, nlayers, W, scale, shift, Kpad, Cout, relu, pool, out, ldo, col0, tap_layer, tap_out, tap_ld, stream);
+int g4d::mlp_chain_bf16_run(const StackCall &c, hipStream_t st) {
+    // large launches of config 3's last level: fp_head_bf16.hip (bit-identical; with c.unknown_grid over the rows in cell order -- the only kernel of
+    // this family that walks them so) ...
+    const bool head = c.mode == LOAD_INTERP && c.in.known_feats && c.in.dist2 && c.in.nn_idx && has_layer_arrays(c);
+    if (const int rc = head ? fp_head_bf16_try(c, st) : -1; rc != -1) return rc;
+    // ... and of its SA levels: sa_group_bf16.hip (bit-identical)
+    if (const int rc = c.mode == LOAD_GROUP && has_layer_arrays(c) ? sa_group_bf16_try(c, st) : -1; rc != -1) return rc;
+    return chain_bf16_impl(c, 1, st);
 }
 
-extern "C" int g4d_mlp_chain_cells_bf16(int mode, long long rows, int K0, const float *X, int ldx, int N, int P, int S, int C, int use_xyz,
-                                        const float *xyz, const float *new_xyz, const float *feats, const int *idx, int n, int m, int C2,
-                                        int C1, const float *known_feats, const float *skip, const float *dist2, const int *nn_idx,
-                                        int nlayers, const unsigned short *const *W, const float *const *scale, const float *const *shift,
-                                        const int *Kpad, const int *Cout, const int *relu, int pool, float *out, int ldo, int col0,
-                                        int tap_layer, float *tap_out, int tap_ld, const void *unknown_grid, g4d_stream_t stream) {
-    if (mode == LOAD_INTERP && unknown_grid && n > 0 && known_feats && dist2 && nn_idx && W && scale && shift && Kpad && Cout && relu && out) {
-        size_t off = 0, stride = 0;
-        grid_sorted_layout(n, &off, &stride);
-        const int rc = fp_head_bf16_try(rows, n, m, C2, C1, known_feats, dist2, nn_idx, nlayers, W, scale, shift, Kpad, Cout, relu, pool, out, ldo, col0, tap_layer,
-                                        tap_out, tap_ld, reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const unsigned char *>(unknown_grid) + off, stride);
-        if (rc != -1) return rc;
-    }
-    return g4d_mlp_chain_bf16(mode, rows, K0, X, ldx, N, P, S, C, use_xyz, xyz, new_xyz, feats, idx, n, m, C2, C1, known_feats, skip, dist2, nn_idx, nlayers, W, scale,
-                              shift, Kpad, Cout, relu, pool, out, ldo, col0, tap_layer, tap_out, tap_ld, stream);
-}
-
-extern "C" int g4d_mlp_chain_bf16x3(int mode, long long rows, int K0, const float *X, int ldx, int N, int P, int S, int C, int use_xyz,
-                                    const float *xyz, const float *new_xyz, const float *feats, const int *idx, int n, int m, int C2,
-                                    int C1, const float *known_feats, const float *skip, const float *dist2, const int *nn_idx,
-                                    int nlayers, const unsigned short *const *W3, const float *const *scale, const float *const *shift,
-                                    const int *Kpad, const int *Cout, const int *relu, int pool, float *out, int ldo, int col0,
-                                    int tap_layer, float *tap_out, int tap_ld, g4d_stream_t stream) {
-    return chain_bf16_impl("g4d_mlp_chain_bf16x3", 3, mode, rows, K0, X, ldx, N, P, S, C, use_xyz, xyz, new_xyz, feats, idx, n, m, C2, C1, known_feats, skip,
-                           dist2, nn_idx, nlayers, W3, scale, shift, Kpad, Cout, relu, pool, out, ldo, col0, tap_layer, tap_out, tap_ld, stream);
-}
+int g4d::mlp_chain_bf16x3_run(const StackCall &c, hipStream_t st) { return chain_bf16_impl(c, 3, st); }

@@ -1,6 +1,7 @@
 // Shared pieces of the MFMA shared-MLP kernels (mlp.hip: one layer per launch; mlp_stack.hip: up to four layers
 // per launch with activations resident in LDS): argument block, per-row loader state and the element loader of
-// the four A-operand sources (DIRECT / GROUP / INTERP / CSR).
+// the four A-operand sources (DIRECT / GROUP / INTERP / CSR) -- and, for the host side of the whole-stack launchers,
+// the call description they all take (StackCall) with the checks they share.
 #pragma once
 #include "g4d_common.h"
 
@@ -88,33 +89,75 @@ bool gemm_narrow_try(const LinearArgs &a, hipStream_t s, int *rc);   // gemm_nar
 // gemm_tile.hip: 128 x 128-tile GEMM for tall DIRECT launches with a deep contraction; same contract
 bool gemm_tile_try(const LinearArgs &a, hipStream_t s, int *rc);
 
-// fp_table.hip: persistent, software-pipelined form of g4d_mlp_chain_table(_cells)_f32 for the 128 -> 64 -> 32 -> <= 16 stack; -1 = not its kind
-int fp_table_try(long long rows, int n, int m, int C2, const float *table, const float *dist2, const int *nn_idx, const void *perm_rec,
-                 size_t perm_stride, const float *pre_scale, const float *pre_shift, float *in_tap, int nlayers, const float *const *W,
-                 const float *const *scale, const float *const *shift, const int *Kpad, const int *Cout, const int *relu, float *out, int ldo,
-                 int col0, int tap_layer, float *tap_out, int tap_ld, hipStream_t st);
+// ---- the host side of a whole-stack launch --------------------------------------------------------------------------------------------
+// ONE description of the call, from the C entry point down to the kernel launch: g4d_mlp_run and the positional entry points (api.hip) build it
+// from a g4d_mlp_args, the table entry points (mlp_chain.hip) by naming the fields they set; the launchers and the persistent-kernel hooks below
+// read it.  `in` reaches the kernels as it stands, apart from `rows` (checked against the family's limit first) and `S` (kept as the caller
+// gave it -- the checks and the hooks look at that value -- and raised to 1 for the kernels): kernel_in().
+struct StackCall {
+    const char *name;   // the entry point that error texts speak of
+    int mode;
+    long long rows;
+    LinearArgs in;      // loaders, pooling and output window; in.K = the first layer's input width
+    int nlayers;        // HOST arrays of nlayers (W: 3 * nlayers pointers -- hi | mid | lo -- for g4d_mlp_chain_bf16x3)
+    const void *const *W;
+    const float *const *scale, *const *shift;
+    const int *Kpad, *Cout, *relu;
+    int tap_layer;      // with tap_out: the hidden layer whose output is also stored to HBM
+    float *tap_out;
+    int tap_ld;
+    const void *unknown_grid;   // INTERP: ball-grid workspace of the unknown cloud, rows walked in its cell order (or NULL)
+    void *ws;                   // g4d_mlp_chain_group_table_ws_f32: scratch of sa_table.hip's work list (g4d_sa_table_ws_bytes)
+    long long ws_bytes;
+};
+inline bool has_layer_arrays(const StackCall &c) { return c.W && c.scale && c.shift && c.Kpad && c.Cout && c.relu && c.in.out; }
+inline int tap_layer_of(const StackCall &c) { return c.tap_out ? c.tap_layer : -1; }
+// LinearArgs::perm_rec (and *stride = perm_stride) of a launch whose rows walk the cell order of c.unknown_grid; no grid: NULL, rows in place
+inline const unsigned char *cell_records(const StackCall &c, size_t *stride) {
+    size_t off = 0;
+    *stride = 0;
+    if (!c.unknown_grid) return nullptr;
+    grid_sorted_layout(c.in.n, &off, stride);
+    return static_cast<const unsigned char *>(c.unknown_grid) + off;
+}
+inline LinearArgs kernel_in(const StackCall &c) {
+    LinearArgs in = c.in;
+    in.rows = (int)c.rows;
+    in.S = c.in.S > 0 ? c.in.S : 1;
+    return in;
+}
 
-// fp_init.hip: persistent form of g4d_mlp_chain_interp_init_f32 for the skip 96 -> 256 -> 128 -> 128 stack, weights shared through LDS; -1 = not its kind
-int fp_init_try(long long rows, int n, int m, int C1, const float *skip, const float *table, int tab_ld, const float *dist2, const int *nn_idx, int nlayers,
-                const float *const *W, const float *const *scale, const float *const *shift, const int *Kpad, const int *Cout, const int *relu, float *out,
-                int ldo, int col0, int tap_layer, float *tap_out, int tap_ld, hipStream_t st);
+// The checks the families share (api.hip), with what differs between them.  Mode, layer count, sizes | rows == 0: kEmptyLaunch, the launcher
+// returns G4D_OK | array pointers, supported widths, pool window, every layer's pointers and padding, the tap.  A family's own checks run after.
+constexpr int kEmptyLaunch = -2;   // private, like the hooks' -1 ("not its kind"): neither may leave through an extern "C" entry point
+struct StackRules {
+    const char *bad_mode;   // text of the mode check
+    bool csr;               // mode 3 allowed
+    int max_layers;         // 0: g4d_mlp_chain_supported() decides (register-chain kernels)
+    long long max_rows;     // rows < max_rows
+    int kpad_multiple, w_pieces;   // (w_pieces: weight pointers per layer)
+};
+int stack_call_check(const StackCall &c, const StackRules &r);
 
-// fp_head_bf16.hip: persistent form of g4d_mlp_chain_bf16 (interpolating mode) for the 128 -> 128 -> 64 -> 32 -> <= 16 stack of config 3; -1 = not its kind
-int fp_head_bf16_try(long long rows, int n, int m, int C2, int C1, const float *known_feats, const float *dist2, const int *nn_idx, int nlayers,
-                     const unsigned short *const *W, const float *const *scale, const float *const *shift, const int *Kpad, const int *Cout,
-                     const int *relu, int pool, float *out, int ldo, int col0, int tap_layer, float *tap_out, int tap_ld, hipStream_t st,
-                     const void *perm_rec = nullptr, size_t perm_stride = 0);   // perm_rec: walk the rows in the cell order of the unknown cloud's grid records
+// the kernel families behind g4d_mlp_run, each in the file of its name (mlp_chain_bf16_run with c.unknown_grid: g4d_mlp_chain_cells_bf16)
+int mlp_stack_f32_run(const StackCall &c, hipStream_t st);
+int mlp_stack_bf16_run(const StackCall &c, hipStream_t st);
+int mlp_wave_f32_run(const StackCall &c, hipStream_t st);
+int mlp_chain_f32_run(const StackCall &c, hipStream_t st);
+int mlp_chain_bf16_run(const StackCall &c, hipStream_t st);
+int mlp_chain_bf16x3_run(const StackCall &c, hipStream_t st);
 
-// sa_group_bf16.hip: persistent form of g4d_mlp_chain_bf16 (grouping mode) for the encoder's three-layer SA stacks
-int sa_group_bf16_try(long long rows, int N, int P, int S, int C, int use_xyz, const float *xyz, const float *new_xyz, const float *feats,
-                      const int *idx, int nlayers, const unsigned short *const *W, const float *const *scale, const float *const *shift,
-                      const int *Kpad, const int *Cout, const int *relu, int pool, float *out, int ldo, int col0, float *tap_out, hipStream_t st);
-
-// sa_table.hip: persistent, software-pipelined form of g4d_mlp_chain_group_table_f32 for large launches (same arguments); -1 = not its kind
-int sa_table_try(long long rows, int N, int P, int S, const float *xyz, const float *new_xyz, const int *idx, const float *table, int tab_ld, int Kt,
-                 const float *tab_wx, const float *pre_scale, const float *pre_shift, int nlayers, const float *const *W, const float *const *scale,
-                 const float *const *shift, const int *Kpad, const int *Cout, const int *relu, int pool, float *out, int ldo, int col0, hipStream_t st,
-                 void *ws = nullptr, long long ws_bytes = 0);   // ws: scratch for the work list that skips blocks of ball-query padding (g4d_sa_table_ws_bytes)
+// The persistent forms of the register-chain launches: each takes the launch when it is its kind and returns -1 when it is not.
+// fp_table.hip: g4d_mlp_chain_table(_cells)_f32 for the 128 -> 64 -> 32 -> <= 16 stack, software-pipelined; c.unknown_grid: rows in cell order
+int fp_table_try(const StackCall &c, hipStream_t st);
+// fp_init.hip: g4d_mlp_chain_interp_init_f32 for the skip 96 -> 256 -> 128 -> 128 stack, weights shared through LDS
+int fp_init_try(const StackCall &c, hipStream_t st);
+// fp_head_bf16.hip: g4d_mlp_chain_bf16 (interpolating mode) for the 128 -> 128 -> 64 -> 32 -> <= 16 stack of config 3; c.unknown_grid as above
+int fp_head_bf16_try(const StackCall &c, hipStream_t st);
+// sa_group_bf16.hip: g4d_mlp_chain_bf16 (grouping mode) for the encoder's three-layer SA stacks
+int sa_group_bf16_try(const StackCall &c, hipStream_t st);
+// sa_table.hip: g4d_mlp_chain_group_table_f32 for large launches, software-pipelined; c.ws: scratch for the work list that skips blocks of padding
+int sa_table_try(const StackCall &c, hipStream_t st);
 
 template <int MODE>
 struct RowCtx {  // per-thread, per-row state reused across K chunks

@@ -212,38 +212,17 @@ __global__ void __launch_bounds__(512) mlp_stack_bf16_kernel(const StackArgsH s)
 
 using namespace g4d;
 
-// One C entry point for all loaders: `mode` 0 DIRECT, 1 GROUP, 2 INTERP, 3 CSR; loader pointers that a mode does
-// not use are ignored.  Layer descriptors arrive as parallel arrays (host memory) of length nlayers <= 4.
-extern "C" int g4d_mlp_stack_bf16(int mode, long long rows, int K0,
-                                 /* DIRECT / CSR */ const float *X, int ldx,
-                                 /* GROUP  */ int N, int P, int S, int C, int use_xyz, const float *xyz, const float *new_xyz,
-                                 const float *feats, const int *idx,
-                                 /* INTERP */ int n, int m, int C2, int C1, const float *known_feats, const float *skip,
-                                 const float *dist2, const int *nn_idx,
-                                 /* CSR    */ int Vg, const int *rowptr, const int *colidx, const float *vals,
-                                 /* layers */ int nlayers, const unsigned short *const *W, const float *const *scale,
-                                 const float *const *shift, const int *Kpad, const int *Cout, const int *relu,
-                                 /* output */ int pool, float *out, int ldo, int col0, int tap_layer, float *tap_out, int tap_ld,
-                                 g4d_stream_t stream) {
-    G4D_REQUIRE(mode >= 0 && mode <= 3, "g4d_mlp_stack_bf16: bad mode");
-    G4D_REQUIRE(nlayers >= 1 && nlayers <= kMaxLayersH, "g4d_mlp_stack_bf16: 1..%d layers", kMaxLayersH);
-    G4D_REQUIRE(rows >= 0 && rows < (1ll << 31) && K0 > 0, "g4d_mlp_stack_bf16: bad sizes");
-    if (rows == 0) return G4D_OK;
-    G4D_REQUIRE(W && scale && shift && Kpad && Cout && relu && out, "g4d_mlp_stack_bf16: null pointer");
-    G4D_REQUIRE(pool >= 0 && pool <= 2, "g4d_mlp_stack_bf16: pool must be 0|1|2");
-    if (pool) G4D_REQUIRE((S == 4 || S == 8 || S == 16 || S == 32 || S == 64) && rows % S == 0, "g4d_mlp_stack_bf16: pooling needs S in {4,8,16,32,64}");
+int g4d::mlp_stack_bf16_run(const StackCall &c, hipStream_t st) {
+    static const StackRules rules = {"bad mode", true, kMaxLayersH, 1ll << 31, 32, 1};
+    if (const int rc = stack_call_check(c, rules)) return rc == kEmptyLaunch ? G4D_OK : rc;
+    const int nlayers = c.nlayers, *Kpad = c.Kpad, *Cout = c.Cout;
     StackArgsH s = {};
-    s.in.rows = (int)rows; s.in.K = K0; s.in.out = out; s.in.ldo = ldo; s.in.col0 = col0; s.in.pool = pool; s.in.S = S > 0 ? S : 1;
-    s.in.X = X; s.in.ldx = ldx;
-    s.in.xyz = xyz; s.in.new_xyz = new_xyz; s.in.feats = feats; s.in.idx = idx; s.in.N = N; s.in.P = P; s.in.C = C; s.in.use_xyz = use_xyz;
-    s.in.known_feats = known_feats; s.in.skip = skip; s.in.dist2 = dist2; s.in.nn_idx = nn_idx; s.in.C2 = C2; s.in.C1 = C1; s.in.m = m; s.in.n = n;
-    s.in.rowptr = rowptr; s.in.colidx = colidx; s.in.vals = vals; s.in.Vg = Vg;
+    s.in = kernel_in(c);
     s.nlayers = nlayers;
     int w0 = 0, w1 = 0;  // widths (floats) buffer 0 / 1 must hold: layer l reads Kpad[l] columns of buffer l&1
     for (int l = 0; l < nlayers; ++l) {
-        G4D_REQUIRE(W[l] && scale[l] && shift[l] && Kpad[l] % 32 == 0 && Cout[l] > 0, "g4d_mlp_stack_bf16: bad layer %d", l);
-        s.layer[l].W = W[l]; s.layer[l].scale = scale[l]; s.layer[l].shift = shift[l];
-        s.layer[l].Kpad = Kpad[l]; s.layer[l].Cout = Cout[l]; s.layer[l].relu = relu[l];
+        s.layer[l].W = static_cast<const unsigned short *>(c.W[l]); s.layer[l].scale = c.scale[l]; s.layer[l].shift = c.shift[l];
+        s.layer[l].Kpad = Kpad[l]; s.layer[l].Cout = Cout[l]; s.layer[l].relu = c.relu[l];
         int &win = (l & 1) ? w1 : w0;
         win = win > Kpad[l] ? win : Kpad[l];
         if (l > 0) {
@@ -251,16 +230,13 @@ extern "C" int g4d_mlp_stack_bf16(int mode, long long rows, int K0,
             G4D_REQUIRE(Kpad[l] <= prev_pad64 && Kpad[l] >= Cout[l - 1], "g4d_mlp_stack_bf16: layer %d K does not chain", l);
         }
     }
-    G4D_REQUIRE(Kpad[0] >= K0, "g4d_mlp_stack_bf16: Kpad[0] < K0");
+    G4D_REQUIRE(Kpad[0] >= c.in.K, "g4d_mlp_stack_bf16: Kpad[0] < K0");
     s.ld0 = w0 + 8;  // bf16 elements; +16 bytes spreads the ds_read_b128 fragment reads over the banks
     s.ld1 = w1 + 8;
     const size_t lds = sizeof(unsigned short) * 64 * (size_t)(s.ld0 + s.ld1);
     G4D_REQUIRE(lds <= 150 * 1024, "g4d_mlp_stack_bf16: stack too wide for LDS (%zu bytes)", lds);
-    s.tap_layer = tap_out ? tap_layer : -1;
-    s.tap_out = tap_out; s.tap_ld = tap_ld;
-    G4D_REQUIRE(s.tap_layer < nlayers - 1, "g4d_mlp_stack_bf16: tap must be a hidden layer");
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    dim3 grid((unsigned)((rows + 63) / 64)), block(512);
+    s.tap_layer = tap_layer_of(c); s.tap_out = c.tap_out; s.tap_ld = c.tap_ld;
+    dim3 grid((unsigned)((c.rows + 63) / 64)), block(512);
 #define G4D_LAUNCH_STACKH(M)                                                                                        \
     {                                                                                                              \
         static unsigned long long attr = 0; /* one bit per device */                                               \
@@ -268,7 +244,7 @@ extern "C" int g4d_mlp_stack_bf16(int mode, long long rows, int K0,
                                               "g4d_mlp_stack_bf16")) return rc;                                    \
         hipLaunchKernelGGL(mlp_stack_bf16_kernel<M>, grid, block, lds, st, s);                                          \
     }
-    switch (mode) {
+    switch (c.mode) {
         case LOAD_DIRECT: G4D_LAUNCH_STACKH(LOAD_DIRECT) break;
         case LOAD_GROUP: G4D_LAUNCH_STACKH(LOAD_GROUP) break;
         case LOAD_INTERP: G4D_LAUNCH_STACKH(LOAD_INTERP) break;

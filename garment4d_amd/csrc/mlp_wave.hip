@@ -210,44 +210,30 @@ __global__ void __launch_bounds__(256, 3) mlp_wave_kernel(const WaveArgs s) {
 
 using namespace g4d;
 
-// Same argument convention as g4d_mlp_stack_f32 (minus the tap); hidden widths must be <= 64.
-extern "C" int g4d_mlp_wave_f32(int mode, long long rows, int K0, const float *X, int ldx, int N, int P, int S, int C, int use_xyz,
-                                const float *xyz, const float *new_xyz, const float *feats, const int *idx, int n, int m, int C2,
-                                int C1, const float *known_feats, const float *skip, const float *dist2, const int *nn_idx, int Vg,
-                                const int *rowptr, const int *colidx, const float *vals, int nlayers, const float *const *W,
-                                const float *const *scale, const float *const *shift, const int *Kpad, const int *Cout,
-                                const int *relu, int pool, float *out, int ldo, int col0, g4d_stream_t stream) {
-    G4D_REQUIRE(mode >= 0 && mode <= 3, "g4d_mlp_wave_f32: bad mode");
-    G4D_REQUIRE(nlayers >= 1 && nlayers <= kWaveLayers, "g4d_mlp_wave_f32: 1..%d layers", kWaveLayers);
-    G4D_REQUIRE(rows >= 0 && rows < (1ll << 31) && K0 > 0, "g4d_mlp_wave_f32: bad sizes");
-    if (rows == 0) return G4D_OK;
-    G4D_REQUIRE(W && scale && shift && Kpad && Cout && relu && out, "g4d_mlp_wave_f32: null pointer");
-    G4D_REQUIRE(pool >= 0 && pool <= 2, "g4d_mlp_wave_f32: pool must be 0|1|2");
-    if (pool) G4D_REQUIRE((S == 4 || S == 8 || S == 16 || S == 32 || S == 64) && rows % S == 0, "g4d_mlp_wave_f32: pooling needs S in {4,8,16,32,64}");
+// Same loaders as the LDS-resident stack, no tap; hidden widths must be <= 64.
+int g4d::mlp_wave_f32_run(const StackCall &c, hipStream_t st) {
+    G4D_REQUIRE(!c.tap_out, "g4d_mlp_run(G4D_MLP_WAVE_F32): the wave-autonomous kernel has no tap");
+    static const StackRules rules = {"bad mode", true, kWaveLayers, 1ll << 31, 32, 1};
+    if (const int rc = stack_call_check(c, rules)) return rc == kEmptyLaunch ? G4D_OK : rc;
+    const int nlayers = c.nlayers, *Kpad = c.Kpad, *Cout = c.Cout;
     WaveArgs s = {};
-    s.in.rows = (int)rows; s.in.K = K0; s.in.out = out; s.in.ldo = ldo; s.in.col0 = col0; s.in.pool = pool; s.in.S = S > 0 ? S : 1;
-    s.in.X = X; s.in.ldx = ldx;
-    s.in.xyz = xyz; s.in.new_xyz = new_xyz; s.in.feats = feats; s.in.idx = idx; s.in.N = N; s.in.P = P; s.in.C = C; s.in.use_xyz = use_xyz;
-    s.in.known_feats = known_feats; s.in.skip = skip; s.in.dist2 = dist2; s.in.nn_idx = nn_idx; s.in.C2 = C2; s.in.C1 = C1; s.in.m = m; s.in.n = n;
-    s.in.rowptr = rowptr; s.in.colidx = colidx; s.in.vals = vals; s.in.Vg = Vg;
+    s.in = kernel_in(c);
     s.nlayers = nlayers;
     int width = 32;  // layer 0 stages 32 columns at a time
     for (int l = 0; l < nlayers; ++l) {
-        G4D_REQUIRE(W[l] && scale[l] && shift[l] && Kpad[l] % 32 == 0 && Cout[l] > 0, "g4d_mlp_wave_f32: bad layer %d", l);
-        s.layer[l].W = W[l]; s.layer[l].scale = scale[l]; s.layer[l].shift = shift[l];
-        s.layer[l].Kpad = Kpad[l]; s.layer[l].Cout = Cout[l]; s.layer[l].relu = relu[l];
+        s.layer[l].W = static_cast<const float *>(c.W[l]); s.layer[l].scale = c.scale[l]; s.layer[l].shift = c.shift[l];
+        s.layer[l].Kpad = Kpad[l]; s.layer[l].Cout = Cout[l]; s.layer[l].relu = c.relu[l];
         if (l > 0) {
             G4D_REQUIRE(Cout[l - 1] <= 64 && Kpad[l] <= 64 && Kpad[l] >= Cout[l - 1], "g4d_mlp_wave_f32: hidden width of layer %d > 64", l - 1);
             width = width > Kpad[l] ? width : Kpad[l];
         }
     }
-    G4D_REQUIRE(Kpad[0] >= K0, "g4d_mlp_wave_f32: Kpad[0] < K0");
+    G4D_REQUIRE(Kpad[0] >= c.in.K, "g4d_mlp_wave_f32: Kpad[0] < K0");
     s.ld = width + 4;
     const size_t lds = sizeof(float) * 4 * 64 * (size_t)s.ld;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const long long tiles = (rows + 63) / 64;
+    const long long tiles = (c.rows + 63) / 64;
     dim3 grid((unsigned)((tiles + 3) / 4)), block(256);
-    switch (mode) {
+    switch (c.mode) {
         case LOAD_DIRECT: hipLaunchKernelGGL(mlp_wave_kernel<LOAD_DIRECT>, grid, block, lds, st, s); break;
         case LOAD_GROUP: hipLaunchKernelGGL(mlp_wave_kernel<LOAD_GROUP>, grid, block, lds, st, s); break;
         case LOAD_INTERP: hipLaunchKernelGGL(mlp_wave_kernel<LOAD_INTERP>, grid, block, lds, st, s); break;

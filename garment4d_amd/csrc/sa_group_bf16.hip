@@ -283,24 +283,25 @@ static int sa_group_bf16_launch(const SaGrpHArgs &a, hipStream_t st) {
 
 // Takes the launch if it is one of the instantiated stacks and large enough to pipeline; returns -1 when it is not (the caller then runs the
 // register-chain kernel), else the launch status.
-int g4d::sa_group_bf16_try(long long rows, int N, int P, int S, int C, int use_xyz, const float *xyz, const float *new_xyz, const float *feats,
-                           const int *idx, int nlayers, const unsigned short *const *W, const float *const *scale, const float *const *shift,
-                           const int *Kpad, const int *Cout, const int *relu, int pool, float *out, int ldo, int col0, float *tap_out, hipStream_t st) {
+int g4d::sa_group_bf16_try(const StackCall &c, hipStream_t st) {
+    const LinearArgs &in = c.in;
+    const unsigned short *const *W = reinterpret_cast<const unsigned short *const *>(c.W);
+    const int S = in.S, C = in.C;
     const int on = (int)tuning("sa_group_bf16_persistent", 1);                 // A/B switch
     const long long min_rows = tuning("sa_group_bf16_min_rows", 262144);
-    if (!on || rows < min_rows || rows >= (1ll << 31) - 64 || nlayers != 3 || pool != 1 || !use_xyz || tap_out || S <= 0 || rows % S != 0 || P <= 0) return -1;
-    if (!relu[0] || !relu[1] || !relu[2] || Cout[1] != Cout[0] || Cout[2] != 2 * Cout[0] || (C > 0 && !feats) || !xyz || !new_xyz || !idx) return -1;
-    const int T1 = Cout[0] / 16;
-    if (Cout[0] % 16 != 0 || Kpad[0] != 32 * (C / 32 + 1) || C % 32 != 0 || Kpad[1] != 32 * ((T1 + 1) / 2) || Kpad[2] != Kpad[1]) return -1;
-    if ((rows / S / P) * (long long)N * (C > 3 ? C : 3) >= (1ll << 32)) return -1;   // 32-bit element offsets
-    G4D_REQUIRE(out && W[0] && W[1] && W[2] && scale[0] && scale[1] && scale[2] && shift[0] && shift[1] && shift[2], "g4d_mlp_chain_bf16: null pointer");
-    G4D_REQUIRE(N > 0 && rows % ((long long)P * S) == 0 && ldo >= col0 + Cout[2] && col0 >= 0, "g4d_mlp_chain_bf16: rows must be clouds x P x S and the output window [%d, %d) must fit ldo = %d",
-                col0, col0 + Cout[2], ldo);
+    if (!on || c.rows < min_rows || c.rows >= (1ll << 31) - 64 || c.nlayers != 3 || in.pool != 1 || !in.use_xyz || c.tap_out || S <= 0 || c.rows % S != 0 || in.P <= 0) return -1;
+    if (!c.relu[0] || !c.relu[1] || !c.relu[2] || c.Cout[1] != c.Cout[0] || c.Cout[2] != 2 * c.Cout[0] || (C > 0 && !in.feats) || !in.xyz || !in.new_xyz || !in.idx) return -1;
+    const int T1 = c.Cout[0] / 16;
+    if (c.Cout[0] % 16 != 0 || c.Kpad[0] != 32 * (C / 32 + 1) || C % 32 != 0 || c.Kpad[1] != 32 * ((T1 + 1) / 2) || c.Kpad[2] != c.Kpad[1]) return -1;
+    if ((c.rows / S / in.P) * (long long)in.N * (C > 3 ? C : 3) >= (1ll << 32)) return -1;   // 32-bit element offsets
+    G4D_REQUIRE(in.out && W[0] && W[1] && W[2] && c.scale[0] && c.scale[1] && c.scale[2] && c.shift[0] && c.shift[1] && c.shift[2], "g4d_mlp_chain_bf16: null pointer");
+    G4D_REQUIRE(in.N > 0 && c.rows % ((long long)in.P * S) == 0 && in.ldo >= in.col0 + c.Cout[2] && in.col0 >= 0, "g4d_mlp_chain_bf16: rows must be clouds x P x S and the output window [%d, %d) must fit ldo = %d",
+                in.col0, in.col0 + c.Cout[2], in.ldo);
     SaGrpHArgs a;
-    a.rows = (int)rows; a.N = N; a.P = P; a.xyz = xyz; a.new_xyz = new_xyz; a.feats = feats; a.idx = idx;
+    a.rows = (int)c.rows; a.N = in.N; a.P = in.P; a.xyz = in.xyz; a.new_xyz = in.new_xyz; a.feats = in.feats; a.idx = in.idx;
     a.W1 = W[0]; a.W2 = W[1]; a.W3 = W[2];
-    a.sc1 = scale[0]; a.sh1 = shift[0]; a.sc2 = scale[1]; a.sh2 = shift[1]; a.sc3 = scale[2]; a.sh3 = shift[2];
-    a.out = out; a.ldo = ldo; a.col0 = col0;
+    a.sc1 = c.scale[0]; a.sh1 = c.shift[0]; a.sc2 = c.scale[1]; a.sh2 = c.shift[1]; a.sc3 = c.scale[2]; a.sh3 = c.shift[2];
+    a.out = in.out; a.ldo = in.ldo; a.col0 = in.col0;
     if (T1 == 1 && S == 16 && C == 0) return sa_group_bf16_launch<1, 16, 0, 4>(a, st);
     if (T1 == 2 && S == 32 && C == 0) return sa_group_bf16_launch<2, 32, 0, 4>(a, st);
     if (T1 == 2 && S == 16 && C == 96) return sa_group_bf16_launch<2, 16, 96, 4>(a, st);

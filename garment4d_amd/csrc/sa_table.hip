@@ -635,24 +635,24 @@ extern "C" long long g4d_sa_table_ws_bytes(long long rows, int Kt, int S, int po
 
 // Takes the launch if it is one of the instantiated shapes and large enough to pipeline (several row blocks per resident wave);
 // returns -1 when it is not (the caller then runs the register-chain kernel), else the launch status.
-int g4d::sa_table_try(long long rows, int N, int P, int S, const float *xyz, const float *new_xyz, const int *idx, const float *table, int tab_ld,
-                      int Kt, const float *tab_wx, const float *pre_scale, const float *pre_shift, int nlayers, const float *const *W,
-                      const float *const *scale, const float *const *shift, const int *Kpad, const int *Cout, const int *relu, int pool, float *out,
-                      int ldo, int col0, hipStream_t st, void *ws, long long ws_bytes) {
-    if (nlayers != 2 || !g4d_sa_table_supported(rows, Kt, S, pool)) return -1;
-    if (Cout[0] != Kt || Cout[1] != 2 * Kt || !relu[0] || !relu[1] || Kpad[0] != Kt || Kpad[1] != Kt) return -1;
-    if ((long long)(rows / S / P) * N >= (1ll << 31)) return -1;
-    G4D_REQUIRE(xyz && new_xyz && idx && table && tab_wx && pre_scale && pre_shift && out && W[0] && W[1] && scale[0] && scale[1] && shift[0] && shift[1],
+int g4d::sa_table_try(const StackCall &c, hipStream_t st) {
+    const LinearArgs &in = c.in;   // (in.K: the table's width Kt)
+    const float *const *W = reinterpret_cast<const float *const *>(c.W);
+    const int S = in.S, Kt = in.K;
+    if (c.nlayers != 2 || !g4d_sa_table_supported(c.rows, Kt, S, in.pool)) return -1;
+    if (c.Cout[0] != Kt || c.Cout[1] != 2 * Kt || !c.relu[0] || !c.relu[1] || c.Kpad[0] != Kt || c.Kpad[1] != Kt) return -1;
+    if ((long long)(c.rows / S / in.P) * in.N >= (1ll << 31)) return -1;
+    G4D_REQUIRE(in.xyz && in.new_xyz && in.idx && in.tab && in.tab_wx && in.pre_scale && in.pre_shift && in.out && W[0] && W[1] && c.scale[0] && c.scale[1] && c.shift[0] && c.shift[1],
                 "g4d_mlp_chain_group_table_f32: null pointer");
-    G4D_REQUIRE(N > 0 && P > 0 && rows % ((long long)P * S) == 0 && ldo >= col0 + Cout[1] && col0 >= 0 && (tab_ld >= Kt || tab_ld == 0) && tab_ld % 4 == 0,
+    G4D_REQUIRE(in.N > 0 && in.P > 0 && c.rows % ((long long)in.P * S) == 0 && in.ldo >= in.col0 + c.Cout[1] && in.col0 >= 0 && (in.tab_ld >= Kt || in.tab_ld == 0) && in.tab_ld % 4 == 0,
                 "g4d_mlp_chain_group_table_f32: rows must be clouds x P x S, the output window [%d, %d) must fit ldo = %d, the table stride %d must cover %d columns (or be 0)",
-                col0, col0 + Cout[1], ldo, tab_ld, Kt);
+                in.col0, in.col0 + c.Cout[1], in.ldo, in.tab_ld, Kt);
     SaTabArgs a;
-    a.rows = (int)rows; a.N = N; a.P = P; a.xyz = xyz; a.new_xyz = new_xyz; a.idx = idx; a.tab = table; a.tab_ld = tab_ld;
-    a.wx = tab_wx; a.ps = pre_scale; a.pf = pre_shift;
-    a.W2 = W[0]; a.sc2 = scale[0]; a.sh2 = shift[0];
-    a.W3 = W[1]; a.sc3 = scale[1]; a.sh3 = shift[1];
-    a.out = out; a.ldo = ldo; a.col0 = col0;
+    a.rows = (int)c.rows; a.N = in.N; a.P = in.P; a.xyz = in.xyz; a.new_xyz = in.new_xyz; a.idx = in.idx; a.tab = in.tab; a.tab_ld = in.tab_ld;
+    a.wx = in.tab_wx; a.ps = in.pre_scale; a.pf = in.pre_shift;
+    a.W2 = W[0]; a.sc2 = c.scale[0]; a.sh2 = c.shift[0];
+    a.W3 = W[1]; a.sc3 = c.scale[1]; a.sh3 = c.shift[1];
+    a.out = in.out; a.ldo = in.ldo; a.col0 = in.col0;
     if (Kt == 32 && S == 16) return sa_table_launch<32, 16, 2, 1>(a, st);
     if (Kt == 32 && S == 32) return sa_table_launch<32, 32, 2, 1>(a, st);
     if (Kt == 64 && S == 32) return sa_table_launch<64, 32, 2, 1>(a, st);
@@ -660,7 +660,7 @@ int g4d::sa_table_try(long long rows, int N, int P, int S, const float *xyz, con
     if (Kt == 64 && S == 16) return sa_table_launch<64, 16, 1, 1>(a, st);
     const int wide = (int)tuning("sa_table_128", 1);   // A/B switch: the 128-wide stack (weights streamed from L2: 192 KB do not fit LDS)
     if (wide == 2 && Kt == 128 && S == 64) return sa_table_launch<128, 64, 1, 0>(a, st);   // (A/B: every wave streaming its own fragments)
-    if (wide && Kt == 128 && S == 64) return sa_table_launch<128, 64, 1, 2>(a, st, ws, ws_bytes);
-    if (wide && Kt == 128 && S == 32) return sa_table_launch<128, 32, 1, 2>(a, st, ws, ws_bytes);
+    if (wide && Kt == 128 && S == 64) return sa_table_launch<128, 64, 1, 2>(a, st, c.ws, c.ws_bytes);
+    if (wide && Kt == 128 && S == 32) return sa_table_launch<128, 32, 1, 2>(a, st, c.ws, c.ws_bytes);
     return -1;
 }

@@ -338,16 +338,21 @@ def wave_fits(layers, pool, S):
     return layers[0].Kpad == 32 and all(L.Cout <= 64 for L in layers[:-1]) and all(L.Kpad <= 64 for L in layers[1:])
 
 
+def layer_arrays(layers, weight="Wf"):
+    """The six per-layer host arrays of the whole-stack entry points, (W, scale, shift, Kpad, Cout, relu), of packed layers; `weight` names the
+    layout the kernel family reads (Wf | Wf16 | Wc16)."""
+    ptrs = lambda tensors: _lib.host_array(ctypes.c_void_p, [t.data_ptr() for t in tensors])
+    ints = lambda values: _lib.host_array(ctypes.c_int, values)
+    return (ptrs([getattr(L, weight) for L in layers]), ptrs([L.scale for L in layers]), ptrs([L.shift for L in layers]),
+            ints([L.Kpad for L in layers]), ints([L.Cout for L in layers]), ints([L.relu for L in layers]))
+
+
 def mlp_stack(mode, rows, K0, layers, out, col0=0, pool=0, S=1, X=None, ldx=0, group=None, interp=None, csr=None, tap=None, cells_grid=None):
     """One launch for the whole stack.  group = (N,P,C,use_xyz,xyz,new_xyz,feats,idx); interp = (n,m,C2,C1,known,skip,
     dist2,nn_idx); csr = (Vg,rowptr,colidx,vals); tap = (layer_index, tensor2d); cells_grid = the ball-grid workspace of the unknown cloud
     (interpolating bf16 launches may then walk the rows in cell order: same bits, shared neighbours, g4d_mlp_chain_cells_bf16)."""
-    import ctypes
     n = len(layers)
-    PA = ctypes.c_void_p * n
-    IA = ctypes.c_int * n
-    Wp, Sc, Sh = PA(*[L.Wf.data_ptr() for L in layers]), PA(*[L.scale.data_ptr() for L in layers]), PA(*[L.shift.data_ptr() for L in layers])
-    Kp, Co, Re = IA(*[L.Kpad for L in layers]), IA(*[L.Cout for L in layers]), IA(*[L.relu for L in layers])
+    Wp, Sc, Sh, Kp, Co, Re = layer_arrays(layers)
     gN = gP = gC = gU = 0
     gx = gn = gf = gi = 0
     if group is not None:
@@ -364,16 +369,15 @@ def mlp_stack(mode, rows, K0, layers, out, col0=0, pool=0, S=1, X=None, ldx=0, g
         cV, rowptr, colidx, vals = csr
         cr, cc, cv = rowptr.data_ptr(), colidx.data_ptr(), vals.data_ptr()
     tl, tp, tld = (-1, 0, 0) if tap is None else (tap[0], tap[1].data_ptr(), tap[1].shape[-1])
-    vp = lambda arr: ctypes.cast(arr, ctypes.c_void_p)
     # ONE argument block for every kernel family (include/g4d.h g4d_mlp_args / g4d_mlp_run; round 6 -- the seven positional entry points took
     # 34-41 arguments each, mirrored here by hand)
     a = _lib.MlpArgs(mode=mode, K0=K0, rows=rows, X=_ptr(X), ldx=ldx, N=gN, P=gP, S=S, C=gC, use_xyz=gU, xyz=gx, new_xyz=gn, feats=gf, idx=gi,
                      n=inn, m=im, C2=iC2, C1=iC1, known_feats=ik, skip=isk, dist2=idd, nn_idx=ii, Vg=cV, rowptr=cr, colidx=cc, vals=cv, nlayers=n,
-                     scale=vp(Sc), shift=vp(Sh), Kpad=vp(Kp), Cout=vp(Co), relu=vp(Re), pool=pool, out=out.data_ptr(), ldo=out.shape[-1], col0=col0,
+                     scale=Sc, shift=Sh, Kpad=Kp, Cout=Co, relu=Re, pool=pool, out=out.data_ptr(), ldo=out.shape[-1], col0=col0,
                      tap_out=tp, tap_ld=tld)
     a.tap_layer = tl
     def run(family, wptrs):
-        a.W = vp(wptrs)
+        a.W = wptrs
         a._keep = (wptrs, Sc, Sh, Kp, Co, Re)    # the host arrays the block points at live as long as the block (a recorded call may be replayed: scripts/exp_overlap.py)
         _lib.call("g4d_mlp_run", family, ctypes.pointer(a), _lib.stream_ptr())
         return out
@@ -381,11 +385,11 @@ def mlp_stack(mode, rows, K0, layers, out, col0=0, pool=0, S=1, X=None, ldx=0, g
     if current_precision() == "bf16" and chain_fits(layers, pool, S, mode, bf16=True):   # register-chain bf16 kernel: any launch size, no LDS
         if mode == 2 and cells_grid is not None:
             a.unknown_grid = cells_grid.data_ptr()       # rows walked in the cell order of the unknown cloud's grid (same bits)
-        return run(_lib.MLP_CHAIN_BF16, PA(*[L.Wc16.data_ptr() for L in layers]))
+        return run(_lib.MLP_CHAIN_BF16, _lib.host_array(ctypes.c_void_p, [L.Wc16.data_ptr() for L in layers]))
     if current_precision() == "bf16x3" and chain_fits(layers, pool, S, mode, bf16=True):
-        return run(_lib.MLP_CHAIN_BF16X3, (ctypes.c_void_p * (3 * n))(*[t.data_ptr() for L in layers for t in L.Wc16x3()]))
+        return run(_lib.MLP_CHAIN_BF16X3, _lib.host_array(ctypes.c_void_p, [t.data_ptr() for L in layers for t in L.Wc16x3()]))
     if _use_bf16(rows):
-        return run(_lib.MLP_STACK_BF16, PA(*[L.Wf16.data_ptr() for L in layers]))
+        return run(_lib.MLP_STACK_BF16, _lib.host_array(ctypes.c_void_p, [L.Wf16.data_ptr() for L in layers]))
     if current_precision() in ("fp32", "bf16x3") and chain_fits(layers, pool, S, mode, bf16=False):
         return run(_lib.MLP_CHAIN_F32, Wp)
     if tap is None and wave_fits(layers, pool, S):
@@ -698,16 +702,12 @@ def sa_scale_mlp(xyz, new_xyz, feats_pm, idx, layers, use_xyz, pool, out, col0, 
     if table is not None:
         tab, c0, wxT = table
         L0, rest = layers[0], layers[1:]
-        PA, IA = ctypes.c_void_p * len(rest), ctypes.c_int * len(rest)
         # scratch for the widest stack's work list (round 6: blocks of ball-query padding are not computed; csrc/sa_table.hip) -- 0 bytes for every other shape
         nws = int(_lib.lib().g4d_sa_table_ws_bytes(B * P * S, L0.Cout, S, pool)) if len(rest) == 2 else 0
         ws = torch.empty((nws + 3) // 4, dtype=torch.int32, device=xyz.device) if nws > 0 else None
         _lib.call("g4d_mlp_chain_group_table_ws_f32", B * P * S, N, P, S, xyz.data_ptr(), new_xyz.data_ptr(), idx.data_ptr(),
                   tab.data_ptr() + 4 * c0, tab.shape[-1] if tab_ld is None else tab_ld, L0.Cout, wxT.data_ptr(), L0.scale.data_ptr(), L0.shift.data_ptr(), len(rest),
-                  ctypes.cast(PA(*[L.Wf.data_ptr() for L in rest]), ctypes.c_void_p), ctypes.cast(PA(*[L.scale.data_ptr() for L in rest]), ctypes.c_void_p),
-                  ctypes.cast(PA(*[L.shift.data_ptr() for L in rest]), ctypes.c_void_p), ctypes.cast(IA(*[L.Kpad for L in rest]), ctypes.c_void_p),
-                  ctypes.cast(IA(*[L.Cout for L in rest]), ctypes.c_void_p), ctypes.cast(IA(*[L.relu for L in rest]), ctypes.c_void_p),
-                  pool, out.data_ptr(), out.shape[-1], col0, _ptr(ws), nws, stream)
+                  *layer_arrays(rest), pool, out.data_ptr(), out.shape[-1], col0, _ptr(ws), nws, stream)
         return
 
     def first(L, pl, o, c0):
@@ -995,17 +995,13 @@ def fp_forward(fp, unknown, known, unknow_feats_pm, known_feats_pm, head=None, u
             assert table.shape == (B * m, L0.Cout)
             nl = len(layers)
             final = torch.empty((B, n, rest[-1].Cout), dtype=torch.float32, device=unknown.device) if head is not None else out
-            PA, IA = ctypes.c_void_p * len(rest), ctypes.c_int * len(rest)
             tap_layer, tap_t = -1, None
             if head is not None and nl > 1:
                 tap_layer, tap_t = nl - 2, out.view(B * n, -1)      # the FP output is a hidden layer of `rest`
             in_tap = out.view(B * n, -1) if (head is not None and nl == 1) else None     # ... or the loader's own output
             _lib.call(*(("g4d_mlp_chain_table_cells_f32", B * n, n, m, L0.Cout, table.data_ptr(), dist2.data_ptr(), nn_idx.data_ptr(), unknown_grid[0].data_ptr())
                         if cells else ("g4d_mlp_chain_table_f32", B * n, n, m, L0.Cout, table.data_ptr(), dist2.data_ptr(), nn_idx.data_ptr())),
-                      L0.scale.data_ptr(), L0.shift.data_ptr(), _ptr(in_tap), 0 if in_tap is None else in_tap.shape[-1], len(rest),
-                      ctypes.cast(PA(*[L.Wf.data_ptr() for L in rest]), ctypes.c_void_p), ctypes.cast(PA(*[L.scale.data_ptr() for L in rest]), ctypes.c_void_p),
-                      ctypes.cast(PA(*[L.shift.data_ptr() for L in rest]), ctypes.c_void_p), ctypes.cast(IA(*[L.Kpad for L in rest]), ctypes.c_void_p),
-                      ctypes.cast(IA(*[L.Cout for L in rest]), ctypes.c_void_p), ctypes.cast(IA(*[L.relu for L in rest]), ctypes.c_void_p),
+                      L0.scale.data_ptr(), L0.shift.data_ptr(), _ptr(in_tap), 0 if in_tap is None else in_tap.shape[-1], len(rest), *layer_arrays(rest),
                       final.view(B * n, -1).data_ptr(), final.shape[-1], 0, tap_layer, _ptr(tap_t), 0 if tap_t is None else tap_t.shape[-1], stream)
             return (out, final) if head is not None else out
     if (_T().fp_table and C1 > 0 and head is None and len(layers) >= 2 and layers[0].Cout % 16 == 0 and current_precision() == "fp32" and _T().use_chain
@@ -1021,12 +1017,8 @@ def fp_forward(fp, unknown, known, unknow_feats_pm, known_feats_pm, head=None, u
             rest = rest + [also_table]
             tapl, tap_t = len(rest) - 2, out.view(B * n, -1)
             fin = torch.empty((B * n, also_table.Cout), dtype=torch.float32, device=unknown.device)
-        PA, IA = ctypes.c_void_p * len(rest), ctypes.c_int * len(rest)
         _lib.call("g4d_mlp_chain_interp_init_f32", B * n, n, m, C1, unknow_feats_pm.data_ptr(), table.data_ptr(), table.shape[-1], dist2.data_ptr(),
-                  nn_idx.data_ptr(), len(rest), ctypes.cast(PA(*[L.Wf.data_ptr() for L in rest]), ctypes.c_void_p),
-                  ctypes.cast(PA(*[L.scale.data_ptr() for L in rest]), ctypes.c_void_p), ctypes.cast(PA(*[L.shift.data_ptr() for L in rest]), ctypes.c_void_p),
-                  ctypes.cast(IA(*[L.Kpad for L in rest]), ctypes.c_void_p), ctypes.cast(IA(*[L.Cout for L in rest]), ctypes.c_void_p),
-                  ctypes.cast(IA(*[L.relu for L in rest]), ctypes.c_void_p), fin.data_ptr(), fin.shape[-1], 0, tapl, _ptr(tap_t),
+                  nn_idx.data_ptr(), len(rest), *layer_arrays(rest), fin.data_ptr(), fin.shape[-1], 0, tapl, _ptr(tap_t),
                   0 if tap_t is None else tap_t.shape[-1], stream)
         return (out, fin) if tap_t is not None else out
     if head is not None:
