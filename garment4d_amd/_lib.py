@@ -145,6 +145,12 @@ SIGNATURES = {
     "g4d_rodrigues_f32": [_I, _vp, _vp, _vp],
     "g4d_rigid_transform_f32": [_I, _I, _I, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "g4d_lbs_pose_skin_f32": [_I, _I, _I, _I, _vp, _vp, _vp, _vp, _I, _vp, _vp, _vp, _vp],
+    "g4d_taubin_smooth_f32": [_I, _I, _I, _I, _F, _F, _I, _vp, _vp, _vp, _vp, _vp, _vp],
+    "g4d_vertex_normals_area_f32": [_I, _I, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "g4d_mesh_aabb_f32": [_I, _I, _I, _vp, _vp, _vp, _vp],
+    "g4d_mesh_nearest_f32": [_I, _I, _I, _I, _I, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "g4d_depen_targets_f32": [_I, _I, _F, _F, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "g4d_depen_solve_f32": [_I, _I, _I, _I, _I, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
 }
 
 _lib = None

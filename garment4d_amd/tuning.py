@@ -103,6 +103,8 @@ class Tuning:
     lbs_mfma: bool = True              # round 5: matrix-pipe route (g4d_lbs_mfma_f32), taken at every batch size
     lbs_one_launch: bool = True        # round 4's one-launch kernel (when lbs_mfma is off)
     lbs_one_launch_max_b: int = 1 << 30
+    # ---- garment post-processing (postprocess.py)
+    nearest_cull: bool = True          # nearest_on_mesh: a wave skips a block of 64 faces whose box is farther than every lane's best (csrc/mesh_nearest.hip)
     # ---- native keys (include/g4d.h "tuning"): (key, value) pairs applied as per-thread overrides while this Tuning is in force
     native: Tuple[Tuple[str, int], ...] = ()
 
@@ -140,7 +142,7 @@ def from_environment() -> Tuning:
         refine_autograd=_env_flag("G4D_REFINE_AUTOGRAD", d.refine_autograd), mgn_autograd=_env_flag("G4D_MGN_AUTOGRAD", d.mgn_autograd),
         stage1_autograd=_env_flag("G4D_STAGE1_AUTOGRAD", d.stage1_autograd), mlp_autograd=_env_flag("G4D_MLP_AUTOGRAD", d.mlp_autograd),
         dropin_fused=_env_flag("G4D_DROPIN_FUSED", d.dropin_fused), dropin_whole_model=_env_flag("G4D_DROPIN_WHOLE", d.dropin_whole_model), lbs_mfma=_env_flag("G4D_LBS_MFMA", d.lbs_mfma), lbs_one_launch=_env_flag("G4D_LBS_ONE", d.lbs_one_launch),
-        lbs_one_launch_max_b=_env_int("G4D_LBS_ONE_MAX_B", d.lbs_one_launch_max_b))
+        lbs_one_launch_max_b=_env_int("G4D_LBS_ONE_MAX_B", d.lbs_one_launch_max_b), nearest_cull=_env_flag("G4D_NEAREST_CULL", d.nearest_cull))
 
 
 DEFAULT = from_environment()

@@ -845,6 +845,68 @@ int g4d_stage1_garment_f32(int b, int bp, int vg, int v, int nf, int pdim, const
                            const int *inc, const float *coeff, const float *coeff_gt, float w_pca, float w_l2, float w_pen, float w_lap, float *ws,
                            float *out, float *grad_pred, float *grad_coeff, g4d_stream_t stream);
 
+/* ---- garment post-processing (utils/post_processing.py:145-228, :299-319): Taubin smoothing and depenetration --------------------------------
+ * What the reference runs on the CPU, one frame at a time, on the last refinement round before it shows a mesh (psbody AABB tree +
+ * scipy spsolve).  psbody is third-party code that cannot be run here: the definitions below are the contract ("Unpinned").
+ * All fp32, point-major, on `stream`; no atomics, every reduction order fixed by the shapes (two runs give the same bits); nothing is read back
+ * to the host.  `frame_active` (frames) int32 or NULL, where it appears: a frame with frame_active[f] == 0 is skipped and its outputs are left
+ * untouched (depenetration hands the previous round's counts in: a frame without a flagged vertex is finished for good).
+ *
+ * g4d_taubin_smooth_f32: `iters` steps  S <- S + c_it * (adj . S),  c_it = lam for even it, mu for odd it (:302-309: lam 0.05, mu -0.052,
+ * 100 steps), adj = D^-1 A - I in CSR, in one launch with the (vg x 4-column) slab of a frame in LDS -- g4d_jacobi_smooth_f32's domain
+ * (vg <= 5104, max_row_entries <= 8, else G4D_EINVAL) and arithmetic: bit-identical to `iters` alternating g4d_spmm_axpy_rows_f32 calls.
+ * S and out may alias. */
+int g4d_taubin_smooth_f32(int frames, int vg, int c, int iters, float lam, float mu, int max_row_entries, const float *S, const int *rowptr,
+                          const int *colidx, const float *vals, float *out, g4d_stream_t stream);
+
+/* Area-weighted unit vertex normals (psbody VertNormals): out (frames,v,3) = s / |s| with s = the sum over the incident faces, in the order of
+ * the (vf_rowptr, vf_fid) CSR, of the SCALED face normals (v1 - v0) x (v2 - v0); |s| = sqrt((sx^2 + sy^2) + sz^2), no fused operation.
+ * NOT g4d_vertex_normals_f32, which sums UNIT face normals.  Deviation: |s| == 0 (an isolated vertex, or faces that cancel) yields the zero
+ * vector where the division would give NaN. */
+int g4d_vertex_normals_area_f32(int frames, int v, const float *verts, const int *faces, const int *vf_rowptr, const int *vf_fid,
+                                const int *frame_active, float *out, g4d_stream_t stream);
+
+/* Nearest point on a triangle mesh, per frame.  faces (nf,3) in ANY order (the caller sorts them once per topology so that 64 consecutive
+ * faces are close together; face_ids (nf) = the index each row has in the caller's own face list, which is what `face` reports and what
+ * breaks ties).  g4d_mesh_aabb_f32 writes boxes (frames, ceil(nf / 64), 6) = {lo xyz, hi xyz} of every block of 64 faces, padded per axis by
+ * 2^-18 * max(|lo|, |hi|); g4d_mesh_nearest_f32 needs them (also with cull == 0) and vnormals (frames,v,3) = g4d_vertex_normals_area_f32.
+ *
+ * Per query q (points (frames,p,3)): the triangle with the smallest dist2, ties to the lowest face id; with a, b, c its corners,
+ *   dot(u, w) = fmaf(u.z, w.z, fmaf(u.y, w.y, u.x * w.x));   every other operation below is a single rounded fp32 operation, never fused
+ *   ab = b - a, ac = c - a;  d1 = dot(ab, q - a), d2 = dot(ac, q - a), d3 = dot(ab, q - b), d4 = dot(ac, q - b), d5 = dot(ab, q - c), d6 = dot(ac, q - c)
+ *   vc = d1 * d4 - d3 * d2,  vb = d5 * d2 - d1 * d6,  va = d3 * d6 - d5 * d4,  e43 = d4 - d3,  e56 = d5 - d6
+ *   part = first that holds of:  4 (vertex a): d1 <= 0 && d2 <= 0;   5 (vertex b): d3 >= 0 && d4 <= d3;   1 (edge ab): vc <= 0 && d1 >= 0 && d3 <= 0;
+ *          6 (vertex c): d6 >= 0 && d5 <= d6;   3 (edge ca): vb <= 0 && d2 >= 0 && d6 <= 0;   2 (edge bc): va <= 0 && e43 >= 0 && e56 >= 0;   else 0 (interior)
+ *   den = (va + vb) + vc | d1 - d3 | e43 + e56 | d2 - d6   for part 0 | 1 | 2 | 3,   r = 1 / den
+ *   w = vc * r | e43 * r | d2 * r | 1   for part 0 | 2 | 3 | 6, else 0;     v = vb * r | d1 * r | 1 - w | 1   for part 0 | 1 | 2 | 5, else 0
+ *   point = (a + ab * v) + ac * w;   dist2 = (dx * dx + dy * dy) + dz * dz  with  d = q - point
+ *   normal: part 0: n = ab x ac, n / sqrt((nx^2 + ny^2) + nz^2) (zero when that length is 0); part 4 / 5 / 6: vnormals of a / b / c;
+ *           part 1 / 2 / 3: vnormals of (a, b) / (b, c) / (c, a) added;  then divided by (its length + 1e-10)  (:175).
+ * A zero-area triangle gives a NaN dist2 and never wins; a mesh of nothing else reports face = part = -1, dist2 = inf, point = NaN, normal = 0.
+ * cull != 0: a wave of 64 queries skips a block of faces whose box is farther from every one of its queries than that query's best so far
+ * ((1 - 2^-18) * gap^2 > best): conservative, so cull 0 and 1 give the same bits.  visited (frames * ceil(p / 64)) int32 or NULL: the number of
+ * face blocks each wave went through (a measurement aid). */
+int g4d_mesh_aabb_f32(int frames, int v, int nf, const float *verts, const int *faces, float *boxes, g4d_stream_t stream);
+int g4d_mesh_nearest_f32(int frames, int p, int v, int nf, int cull, const float *points, const float *verts, const int *faces,
+                         const int *face_ids, const float *boxes, const float *vnormals, const int *frame_active, float *point, float *dist2,
+                         int *face, int *part, float *normal, int *visited, g4d_stream_t stream);
+
+/* One depenetration round (:179-228), after (near_p, near_n) = g4d_mesh_nearest_f32(verts, body) and garment_n = g4d_vertex_normals_area_f32:
+ * g4d_depen_targets_f32, per garment vertex i (products and sums left to right, nothing fused):
+ *   flagged = ((v - p) . n) < 0;   s = sign(m . n) (may be 0);   d = (p - v) * s;
+ *   flagged:  target = p + (eps * d) / (1e-4 + |d|),  w2 = ww * ww;    otherwise:  target = v,  w2 = 1;      counts[f] = number flagged.
+ * g4d_depen_solve_f32: out = x after exactly cg_iters conjugate-gradient steps from x0 = verts on
+ *   (L^T L + diag(w2)) x = L^T L verts + w2 * target
+ * per frame and coordinate (one workgroup each; dot products by a fixed tree over the workgroup), L given as CSR with its transpose,
+ * vg <= 5104 and <= 8 entries per row of either (else G4D_EINVAL).  residual (frames,3) = |b - M x|_2 / |b|_2 at exit, from a fresh product.
+ * A frame with counts[f] == 0 is copied through bit for bit with residual 0 (the reference solves once more and gets verts back up to
+ * rounding).  Error after k steps <= 2 ((sqrt(kappa) - 1) / (sqrt(kappa) + 1))^k in the M-norm, kappa <= ww^2 + |L|_2^2 (M >= I). */
+int g4d_depen_targets_f32(int frames, int vg, float eps, float ww, const float *verts, const float *near_p, const float *near_n,
+                          const float *garment_n, const int *frame_active, float *w2, float *target, int *counts, g4d_stream_t stream);
+int g4d_depen_solve_f32(int frames, int vg, int cg_iters, int max_row_entries, int max_row_entries_t, const float *verts, const float *w2,
+                        const float *target, const int *counts, const int *rowptr, const int *colidx, const float *vals, const int *rowptr_t,
+                        const int *colidx_t, const float *vals_t, float *out, float *residual, g4d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
