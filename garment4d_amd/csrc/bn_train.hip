@@ -17,9 +17,9 @@
 // throughout (the model's widths are multiples of 4 except the 3-wide coordinate input, which no BatchNorm sees).
 //
 // Reductions: the rows are cut into slices of g4d_bn_slice_rows(rows, c) rows (a function of the shape alone); block = slice, a thread adds its
-// rows in ascending order, the TY partials of a column are added in ascending ty, the slice partials go to the workspace and are added by
-// bn_reduce_kernel in a fixed order (four interleaved chains in slice order, then ((0 + 1) + 2) + 3).  Every output is written once; no atomics.
-#include "g4d_common.h"
+// rows in ascending order; the TY partials of a column and then the slice partials are added by reduce.h's slice_col_sums and reduce_slices.
+// Every output is written once; no atomics.
+#include "reduce.h"
 
 namespace g4d {
 
@@ -27,7 +27,6 @@ typedef float bn_f32x4u __attribute__((ext_vector_type(4), aligned(4)));   // 16
 
 constexpr int kBnSliceMin = 64;       // rows of a slice at least
 constexpr int kBnMaxSlices = 1024;    // a CONSTANT, not a device query: 4 blocks per CU on 256 CUs
-constexpr int kBnChains = 4;          // bn_reduce_kernel: interleaved chains per element
 constexpr int kBnRowsPerThread = 8;   // element-wise kernels: rows a thread walks (amortises the per-column constants)
 
 __host__ __device__ inline long long bn_slice_rows(long long rows) {
@@ -85,26 +84,6 @@ __device__ __forceinline__ void bn_store(float *p, const float (&x)[VEC]) {
     }
 }
 
-// The TY partials of a column, added in ascending ty by thread (0, tx); NOUT values per column go to ws[slice][o][c].
-template <int VEC, int NOUT>
-__device__ __forceinline__ void bn_block_sum(float (&acc)[NOUT][VEC], float *part, int tx, int ty, int tx_n, int ty_n, int col, int c, float *__restrict__ ws) {
-#pragma unroll
-    for (int o = 0; o < NOUT; ++o)
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) part[(o * 256 + threadIdx.x) * VEC + j] = acc[o][j];
-    __syncthreads();
-    if (ty == 0 && col < c) {
-#pragma unroll
-        for (int o = 0; o < NOUT; ++o)
-#pragma unroll
-            for (int j = 0; j < VEC; ++j) {
-                float s = part[(o * 256 + tx) * VEC + j];
-                for (int k = 1; k < ty_n; ++k) s += part[(o * 256 + k * tx_n + tx) * VEC + j];
-                ws[((size_t)blockIdx.x * NOUT + o) * c + col + j] = s;
-            }
-    }
-}
-
 // pass 1 (mean == NULL): slice sums of y; pass 2: slice sums of (y - mean)^2
 template <int VEC>
 __global__ void __launch_bounds__(256) bn_stats_kernel(long long rows, long long slice_rows, int c, int tx_n, const float *__restrict__ Y, long long ldy,
@@ -132,34 +111,7 @@ __global__ void __launch_bounds__(256) bn_stats_kernel(long long rows, long long
             }
         }
     }
-    bn_block_sum<VEC, 1>(acc, part, tx, ty, tx_n, ty_n, col, c, ws);
-}
-
-// out0[i] (i < n0) / out1[i - n0] = (sum over the slices of ws[s][i]) / div, fixed order (a division: a column of equal values whose sum is
-// exact has exactly that value as its mean, and variance 0).  Thread (j, x): element 64 * blockIdx.x + x, slices
-// j, j + 4, ... ascending.
-__global__ void __launch_bounds__(256) bn_reduce_kernel(long long slices, int n, int n0, float div, const float *__restrict__ ws, float *__restrict__ out0,
-                                                       float *__restrict__ out1) {
-    __shared__ float part[256];
-    const int x = threadIdx.x & 63, j = threadIdx.x >> 6;
-    const int i = blockIdx.x * 64 + x;
-    float acc = 0.f;
-    if (i < n) {
-        long long s = j;
-        for (; s + 3 * kBnChains < slices; s += 4 * kBnChains) {   // four loads in flight, added in slice order
-            const float a0 = ws[(size_t)s * n + i], a1 = ws[(size_t)(s + kBnChains) * n + i], a2 = ws[(size_t)(s + 2 * kBnChains) * n + i],
-                        a3 = ws[(size_t)(s + 3 * kBnChains) * n + i];
-            acc += a0; acc += a1; acc += a2; acc += a3;
-        }
-        for (; s < slices; s += kBnChains) acc += ws[(size_t)s * n + i];
-    }
-    part[threadIdx.x] = acc;
-    __syncthreads();
-    if (j == 0 && i < n) {
-        const float v = (((part[x] + part[64 + x]) + part[128 + x]) + part[192 + x]) / div;
-        if (i < n0) out0[i] = v;
-        else out1[i - n0] = v;
-    }
+    slice_col_sums<VEC, 1>(acc, part, tx, ty, tx_n, ty_n, col, c, ws);
 }
 
 template <int VEC>
@@ -220,7 +172,7 @@ __global__ void __launch_bounds__(256) bn_grad_reduce_kernel(long long rows, lon
             }
         }
     }
-    bn_block_sum<VEC, 2>(acc, part, tx, ty, tx_n, ty_n, col, c, ws);
+    slice_col_sums<VEC, 2>(acc, part, tx, ty, tx_n, ty_n, col, c, ws);
 }
 
 template <int VEC>
@@ -348,12 +300,12 @@ extern "C" int g4d_bn_stats_f32(long long rows, int c, const float *Y, int ldy, 
     const BnShape s = bn_shape(c);
     G4D_REQUIRE(s.gy <= 65535, "g4d_bn_stats_f32: too wide");
     const long long slices = bn_slices(rows), sr = bn_slice_rows(rows);
-    const dim3 grid((unsigned)slices, s.gy), red((c + 63) / 64);
+    const dim3 grid((unsigned)slices, s.gy);
     for (int pass = 0; pass < 2; ++pass) {
         const float *m = pass ? mean : nullptr;
         if (s.vec) hipLaunchKernelGGL(bn_stats_kernel<4>, grid, dim3(256), 0, st, rows, sr, c, s.tx_n, Y, (long long)ldy, m, ws);
         else hipLaunchKernelGGL(bn_stats_kernel<1>, grid, dim3(256), 0, st, rows, sr, c, s.tx_n, Y, (long long)ldy, m, ws);
-        hipLaunchKernelGGL(bn_reduce_kernel, red, dim3(256), 0, st, slices, c, c, (float)rows, ws, pass ? var : mean, (float *)nullptr);
+        reduce_slices(slices, c, c, (float)rows, ws, pass ? var : mean, nullptr, st);
     }
     return check_launch("g4d_bn_stats_f32");
 }
@@ -393,7 +345,7 @@ extern "C" int g4d_bn_act_grad_reduce_f32(long long rows, int c, const float *dO
     const dim3 grid((unsigned)slices, s.gy);
     if (s.vec) hipLaunchKernelGGL(bn_grad_reduce_kernel<4>, grid, dim3(256), 0, st, rows, sr, c, s.tx_n, dOut, (long long)ldg, Y, (long long)ldy, mean, var, eps, gamma, beta, relu, ws);
     else hipLaunchKernelGGL(bn_grad_reduce_kernel<1>, grid, dim3(256), 0, st, rows, sr, c, s.tx_n, dOut, (long long)ldg, Y, (long long)ldy, mean, var, eps, gamma, beta, relu, ws);
-    hipLaunchKernelGGL(bn_reduce_kernel, dim3((2 * c + 63) / 64), dim3(256), 0, st, slices, 2 * c, c, 1.0f, ws, dgamma, dbeta);
+    reduce_slices(slices, 2 * (long long)c, c, 1.0f, ws, dgamma, dbeta, st);
     return check_launch("g4d_bn_act_grad_reduce_f32");
 }
 

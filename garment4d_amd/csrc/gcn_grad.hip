@@ -19,8 +19,8 @@
 // when Cout <= 32.  Loads run AHEAD - 1 k-steps in front of the MFMAs: AHEAD register slots, each refilled right after it is consumed.
 //
 // Deterministic: the number of slices is a function of (rows, Fin, Cout) alone; every slice writes its partial (Fin x Cout) tile to the
-// workspace and reduce_slices_kernel sums the slices in a fixed order (four interleaved chains, then ((0 + 1) + 2) + 3).  No atomics in this file.
-#include "g4d_common.h"
+// workspace and reduce.h's reduce_slices sums the slices in a fixed order.  No atomics in this file.
+#include "reduce.h"
 
 namespace g4d {
 
@@ -30,7 +30,6 @@ typedef float gg_f32x2u __attribute__((ext_vector_type(2), aligned(4)));
 
 constexpr int kSliceMin = 256;      // rows of a slice at least (any length works: rows behind a slice's end are predicated)
 constexpr int kWorkUnits = 2048;    // slices x channel tiles aimed at: 2 waves on each of the 1024 SIMDs -- a CONSTANT, not a device query
-constexpr int kRedChains = 4;       // reduce_slices_kernel: interleaved chains per element
 
 // rows per slice / number of slices: functions of the shape only
 __host__ __device__ inline long long tn_slice_rows(long long rows, int cout) {
@@ -87,8 +86,8 @@ __global__ void __launch_bounds__(256) spmm_rows_grad_kernel(long long rows, int
 
 // ---- db: column sums of G, two passes ------------------------------------------------------------------------------------------------
 // Block = one slice of the rows; thread (ty, tx): VEC columns from VEC * tx on (one 16-byte load per row when c % 4 == 0), rows ty, ty + TY, ...
-// of the slice; the TY partial sums of a column are added in ascending ty by thread (0, tx).  TX = the power of two >= c / VEC (<= 256);
-// wider matrices take grid.y blocks of 256 * VEC columns.
+// of the slice; the TY partial sums of a column are added by slice_col_sums.  TX = the power of two >= c / VEC (<= 256); wider matrices
+// take grid.y blocks of 256 * VEC columns.
 template <int VEC>
 __global__ void __launch_bounds__(256) col_sum_kernel(long long rows, long long slice_rows, int c, int tx_n, const float *__restrict__ dY,
                                                      const float *__restrict__ Y, float *__restrict__ ws) {
@@ -97,9 +96,9 @@ __global__ void __launch_bounds__(256) col_sum_kernel(long long rows, long long 
     const int col = (blockIdx.y * 256 + tx) * VEC;
     const long long r0 = (long long)blockIdx.x * slice_rows;
     const long long r1 = r0 + slice_rows < rows ? r0 + slice_rows : rows;
-    float acc[VEC];
+    float acc[1][VEC];
 #pragma unroll
-    for (int j = 0; j < VEC; ++j) acc[j] = 0.f;
+    for (int j = 0; j < VEC; ++j) acc[0][j] = 0.f;
     if (col < c)
         for (long long r = r0 + ty; r < r1; r += ty_n) {
             const size_t off = (size_t)r * c + col;
@@ -108,43 +107,12 @@ __global__ void __launch_bounds__(256) col_sum_kernel(long long rows, long long 
                 gg_f32x4u y = {1.f, 1.f, 1.f, 1.f};
                 if (Y) y = *reinterpret_cast<const gg_f32x4u *>(Y + off);
 #pragma unroll
-                for (int j = 0; j < 4; ++j) acc[j] += y[j] > 0.f ? g[j] : 0.f;
+                for (int j = 0; j < 4; ++j) acc[0][j] += y[j] > 0.f ? g[j] : 0.f;
             } else {
-                acc[0] += (!Y || Y[off] > 0.f) ? dY[off] : 0.f;
+                acc[0][0] += (!Y || Y[off] > 0.f) ? dY[off] : 0.f;
             }
         }
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) part[threadIdx.x * VEC + j] = acc[j];
-    __syncthreads();
-    if (ty == 0 && col < c) {
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) {
-            float s = part[tx * VEC + j];
-            for (int k = 1; k < ty_n; ++k) s += part[(k * tx_n + tx) * VEC + j];
-            ws[(size_t)blockIdx.x * c + col + j] = s;
-        }
-    }
-}
-
-// ---- out[i] = sum over slices of ws[s][i], fixed order --------------------------------------------------------------------------------
-// Thread (j, x): element blockIdx.x * 64 + x, slices j, j + 4, j + 8, ... in ascending order; then ((chain 0 + chain 1) + chain 2) + chain 3.
-__global__ void __launch_bounds__(256) reduce_slices_kernel(long long slices, long long n, const float *__restrict__ ws, float *__restrict__ out) {
-    __shared__ float part[256];
-    const int x = threadIdx.x & 63, j = threadIdx.x >> 6;
-    const long long i = (long long)blockIdx.x * 64 + x;
-    float acc = 0.f;
-    if (i < n) {
-        long long s = j;
-        for (; s + 3 * kRedChains < slices; s += 4 * kRedChains) {   // four loads in flight, added in slice order
-            const float a0 = ws[(size_t)s * n + i], a1 = ws[(size_t)(s + kRedChains) * n + i], a2 = ws[(size_t)(s + 2 * kRedChains) * n + i],
-                        a3 = ws[(size_t)(s + 3 * kRedChains) * n + i];
-            acc += a0; acc += a1; acc += a2; acc += a3;
-        }
-        for (; s < slices; s += kRedChains) acc += ws[(size_t)s * n + i];
-    }
-    part[threadIdx.x] = acc;
-    __syncthreads();
-    if (j == 0 && i < n) out[i] = ((part[x] + part[64 + x]) + part[128 + x]) + part[192 + x];
+    slice_col_sums<VEC, 1>(acc, part, tx, ty, tx_n, ty_n, col, c, ws);
 }
 
 // ---- dW = X^T . dS ---------------------------------------------------------------------------------------------------------------------
@@ -314,7 +282,7 @@ extern "C" int g4d_col_sum_rows_f32(long long rows, int c, const float *dY, cons
     const dim3 grid((unsigned)slices, (groups + 255) / 256);
     if (vec) hipLaunchKernelGGL(col_sum_kernel<4>, grid, dim3(256), 0, st, rows, sr, c, tx_n, dY, Y, ws);
     else hipLaunchKernelGGL(col_sum_kernel<1>, grid, dim3(256), 0, st, rows, sr, c, tx_n, dY, Y, ws);
-    hipLaunchKernelGGL(reduce_slices_kernel, dim3((c + 63) / 64), dim3(256), 0, st, slices, (long long)c, ws, db);
+    reduce_slices(slices, c, c, 1.0f, ws, db, nullptr, st);
     return check_launch("g4d_col_sum_rows_f32");
 }
 
@@ -346,6 +314,6 @@ extern "C" int g4d_gemm_tn_f32(long long rows, int fin, int ldx, int cout, const
         else if (tiles == 3) tn_launch<0, 0, 3, 4>(rows, fin, ldx, cout, 128 * full, 128, 1, X, dS, ws, st);
         else if (tiles == 4) tn_launch<0, 0, 4, 4>(rows, fin, ldx, cout, 128 * full, 128, 1, X, dS, ws, st);
     }
-    hipLaunchKernelGGL(reduce_slices_kernel, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, st, slices, n, ws, dW);
+    reduce_slices(slices, n, n, 1.0f, ws, dW, nullptr, st);
     return check_launch("g4d_gemm_tn_f32");
 }

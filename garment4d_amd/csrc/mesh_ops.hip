@@ -8,6 +8,8 @@
 //       1e-6) summed per vertex over the incident faces (torch_scatter sum; order = the CSR order given by the caller),
 //       re-normalised with the same clamp.  One thread per (frame, vertex); faces are recomputed per incident vertex
 //       (3x the flops, no (F, nf, 3) intermediate and no atomics -> deterministic).
+//   vertex_normals_area : psbody's VertNormals (garment4d_amd/postprocess.py) -- the same walk over SCALED face normals
+//       (v1 - v0) x (v2 - v0), normalised once.
 #include "g4d_common.h"
 
 namespace g4d {
@@ -73,26 +75,49 @@ __device__ __forceinline__ void unit_clamped(float &x, float &y, float &z) {
     x /= d; y /= d; z /= d;
 }
 
+// The sum over the incident faces of vertex `vid` (CSR order) of the face normal cross(e01, e02): made unit first (UNIT, compute_vnorms) or
+// left scaled by twice the face's area (psbody's VertNormals).
+template <bool UNIT>
+__device__ __forceinline__ void incident_normal_sum(const float *__restrict__ verts, const int *__restrict__ faces, const int *__restrict__ rowptr,
+                                                    const int *__restrict__ fid, int vid, float &sx, float &sy, float &sz) {
+    sx = 0.f; sy = 0.f; sz = 0.f;
+    for (int e = rowptr[vid]; e < rowptr[vid + 1]; ++e) {
+        const int *tri = faces + (size_t)fid[e] * 3;
+        const float *p0 = verts + (size_t)tri[0] * 3, *p1 = verts + (size_t)tri[1] * 3, *p2 = verts + (size_t)tri[2] * 3;
+        const float ax = p1[0] - p0[0], ay = p1[1] - p0[1], az = p1[2] - p0[2];
+        const float bx = p2[0] - p0[0], by = p2[1] - p0[1], bz = p2[2] - p0[2];
+        float nx = ay * bz - az * by, ny = az * bx - ax * bz, nz = ax * by - ay * bx;
+        if (UNIT) unit_clamped(nx, ny, nz);
+        sx += nx; sy += ny; sz += nz;
+    }
+}
+
 __global__ void __launch_bounds__(256) vertex_normals_kernel(long long total, int v, const float *__restrict__ verts_all,
                                                             const int *__restrict__ faces, const int *__restrict__ rowptr,
                                                             const int *__restrict__ fid, float *__restrict__ out) {
     const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
     if (gid >= total) return;
     const long long f = gid / v;
-    const int vid = (int)(gid - f * v);
-    const float *verts = verts_all + (size_t)f * v * 3;
-    float sx = 0.f, sy = 0.f, sz = 0.f;
-    for (int e = rowptr[vid]; e < rowptr[vid + 1]; ++e) {
-        const int *tri = faces + (size_t)fid[e] * 3;
-        const float *p0 = verts + (size_t)tri[0] * 3, *p1 = verts + (size_t)tri[1] * 3, *p2 = verts + (size_t)tri[2] * 3;
-        const float ax = p1[0] - p0[0], ay = p1[1] - p0[1], az = p1[2] - p0[2];
-        const float bx = p2[0] - p0[0], by = p2[1] - p0[1], bz = p2[2] - p0[2];
-        float nx = ay * bz - az * by, ny = az * bx - ax * bz, nz = ax * by - ay * bx;  // cross(e01, e02)
-        unit_clamped(nx, ny, nz);
-        sx += nx; sy += ny; sz += nz;
-    }
+    float sx, sy, sz;
+    incident_normal_sum<true>(verts_all + (size_t)f * v * 3, faces, rowptr, fid, (int)(gid - f * v), sx, sy, sz);
     unit_clamped(sx, sy, sz);
     out[gid * 3 + 0] = sx; out[gid * 3 + 1] = sy; out[gid * 3 + 2] = sz;
+}
+
+// The area-weighted form: normalised once, the zero vector where the sum has no length; a frame with frame_active[f] == 0 is left untouched.
+__global__ void __launch_bounds__(256) vertex_normals_area_kernel(long long total, int v, const float *__restrict__ verts_all,
+                                                                 const int *__restrict__ faces, const int *__restrict__ rowptr,
+                                                                 const int *__restrict__ fid, const int *__restrict__ frame_active,
+                                                                 float *__restrict__ out) {
+    const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (gid >= total) return;
+    const long long f = gid / v;
+    if (frame_active && frame_active[f] == 0) return;
+    float sx, sy, sz;
+    incident_normal_sum<false>(verts_all + (size_t)f * v * 3, faces, rowptr, fid, (int)(gid - f * v), sx, sy, sz);
+    const float d = sqrtf(sx * sx + sy * sy + sz * sz);
+    const bool ok = d > 0.f;
+    out[gid * 3 + 0] = ok ? sx / d : 0.f; out[gid * 3 + 1] = ok ? sy / d : 0.f; out[gid * 3 + 2] = ok ? sz / d : 0.f;
 }
 
 }  // namespace g4d
@@ -129,6 +154,19 @@ extern "C" int g4d_vertex_normals_f32(int frames, int v, const float *verts, con
     hipLaunchKernelGGL(vertex_normals_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), total, v,
                        verts, faces, vf_rowptr, vf_fid, out);
     return check_launch("g4d_vertex_normals_f32");
+}
+
+extern "C" int g4d_vertex_normals_area_f32(int frames, int v, const float *verts, const int *faces, const int *vf_rowptr, const int *vf_fid,
+                                           const int *frame_active, float *out, g4d_stream_t stream) {
+    using namespace g4d;
+    G4D_REQUIRE(frames >= 0 && v >= 0, "g4d_vertex_normals_area_f32: negative size");
+    const long long total = (long long)frames * v;
+    if (total == 0) return G4D_OK;
+    G4D_REQUIRE(verts && faces && vf_rowptr && vf_fid && out, "g4d_vertex_normals_area_f32: null pointer");
+    G4D_REQUIRE((total + 255) / 256 < (1ll << 31), "g4d_vertex_normals_area_f32: too large");
+    hipLaunchKernelGGL(vertex_normals_area_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), total, v,
+                       verts, faces, vf_rowptr, vf_fid, frame_active, out);
+    return check_launch("g4d_vertex_normals_area_f32");
 }
 
 // Interpenetration penalty of `calc_interpenetration_loss` (smplx/loss/temporal_loss.py:20-46), forward:

@@ -25,30 +25,18 @@
 //   the penetration dot product left to right, as g4d_interpenetration_f32
 //
 // Reduction tree of each of the five sums (depth = the number of additions on the longest path, what the error bound counts):
-//   * workgroup: xor-butterfly over the 64 lanes of each wave (strides 32, 16, 8, 4, 2, 1: 6 levels; a + b == b + a, so every lane holds the
-//     same bits), then wave 0 + wave 1 + wave 2 + wave 3 left to right (3 more);
+//   * workgroup: reduce.h's block_sum over the four waves (depth 9);
 //   * frame:     its ceil(Vg / 256) workgroup partials added left to right by one thread of the finishing workgroup;
 //   * total:     finishing thread t adds the frames t, t + 256, ... in that order, then the same workgroup tree over the 256 threads.
 //   depth = 9 + (ceil(Vg / 256) - 1) + (ceil(F / 256) - 1) + 9.  The order depends on the shape alone: two runs give the same bits.
-#include "g4d_common.h"
+#include "reduce.h"
 
 namespace g4d {
 namespace {
 
 constexpr int kRLBlock = 256;
 constexpr int kRLTerms = 5;   // L2, MSRE, Laplacian, penetration, temporal
-
-__device__ __forceinline__ float rl_block_sum(float v, float *sh) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = v + __shfl_xor(v, m, 64);
-    const int w = threadIdx.x >> 6;
-    __syncthreads();   // sh may still be read by the previous call
-    if ((threadIdx.x & 63) == 0) sh[w] = v;
-    __syncthreads();
-    return ((sh[0] + sh[1]) + sh[2]) + sh[3];
-}
-
-__device__ __forceinline__ float rl_norm3(float x, float y, float z) { return sqrtf((x * x + y * y) + z * z); }
+constexpr int kRLWaves = kRLBlock / 64;
 
 struct RLArgs {
     int frames, t, vg, v, nblk, idx_stride, temporal;
@@ -60,7 +48,7 @@ struct RLArgs {
 };
 
 __global__ void __launch_bounds__(kRLBlock) rl_terms_kernel(RLArgs a) {
-    __shared__ float sh[4];
+    __shared__ float sh[kRLWaves];
     const int f = blockIdx.x / a.nblk, blk = blockIdx.x - f * a.nblk;
     const int i = blk * kRLBlock + threadIdx.x;
     float s_l2 = 0.f, s_ms = 0.f, s_lap = 0.f, s_pen = 0.f, s_tmp = 0.f;
@@ -86,7 +74,7 @@ __global__ void __launch_bounds__(kRLBlock) rl_terms_kernel(RLArgs a) {
         lx = lx + rs * px;
         ly = ly + rs * py;
         lz = lz + rs * pz;
-        s_lap = rl_norm3(lx, ly, lz);
+        s_lap = norm3(lx, ly, lz);
         // penetration (the nearest body vertex is the search's; the clamp only keeps a corrupt index inside the frame)
         int bi = a.nn_idx[(base + i) * a.idx_stride];
         bi = min(max(bi, 0), a.v - 1);
@@ -101,13 +89,13 @@ __global__ void __launch_bounds__(kRLBlock) rl_terms_kernel(RLArgs a) {
             if (t < a.t - 1) {
                 const float *q = pf + (size_t)a.vg * 3 + i * 3;
                 const float ex = px - q[0], ey = py - q[1], ez = pz - q[2];
-                s_tmp = rl_norm3(ex, ey, ez);
+                s_tmp = norm3(ex, ey, ez);
                 if (s_tmp > 0.f) { tx = ex / s_tmp; ty = ey / s_tmp; tz = ez / s_tmp; }
             }
             if (a.grad && t > 0) {
                 const float *q = pf - (size_t)a.vg * 3 + i * 3;
                 const float ex = q[0] - px, ey = q[1] - py, ez = q[2] - pz;
-                const float n = rl_norm3(ex, ey, ez);
+                const float n = norm3(ex, ey, ez);
                 if (n > 0.f) { tx = tx - ex / n; ty = ty - ey / n; tz = tz - ez / n; }
             }
         }
@@ -121,8 +109,8 @@ __global__ void __launch_bounds__(kRLBlock) rl_terms_kernel(RLArgs a) {
             a.grad[e + 2] = (a.c_l2 * dz - m * nz) + a.c_tmp * tz;
         }
     }
-    const float r0 = rl_block_sum(s_l2, sh), r1 = rl_block_sum(s_ms, sh), r2 = rl_block_sum(s_lap, sh), r3 = rl_block_sum(s_pen, sh),
-                r4 = rl_block_sum(s_tmp, sh);
+    const float r0 = block_sum<kRLWaves>(s_l2, sh), r1 = block_sum<kRLWaves>(s_ms, sh), r2 = block_sum<kRLWaves>(s_lap, sh), r3 = block_sum<kRLWaves>(s_pen, sh),
+                r4 = block_sum<kRLWaves>(s_tmp, sh);
     if (threadIdx.x == 0) {
         float *o = a.partials + (size_t)blockIdx.x * kRLTerms;
         o[0] = r0; o[1] = r1; o[2] = r2; o[3] = r3; o[4] = r4;
@@ -152,7 +140,7 @@ __global__ void __launch_bounds__(kRLBlock) rl_lap_grad_kernel(long long total, 
 
 __global__ void __launch_bounds__(kRLBlock) rl_finish_kernel(int frames, int vg, int nblk, const float *__restrict__ partials, float inv_n, float inv_tmp,
                                                              float *__restrict__ out, float *__restrict__ msre_frames) {
-    __shared__ float sh[4];
+    __shared__ float sh[kRLWaves];
     float acc[kRLTerms] = {0.f, 0.f, 0.f, 0.f, 0.f};
     for (int f = threadIdx.x; f < frames; f += kRLBlock) {
         const float *pf = partials + (size_t)f * nblk * kRLTerms;
@@ -169,7 +157,7 @@ __global__ void __launch_bounds__(kRLBlock) rl_finish_kernel(int frames, int vg,
     }
     float r[kRLTerms];
 #pragma unroll
-    for (int c = 0; c < kRLTerms; ++c) r[c] = rl_block_sum(acc[c], sh);
+    for (int c = 0; c < kRLTerms; ++c) r[c] = block_sum<kRLWaves>(acc[c], sh);
     if (threadIdx.x == 0) {
         out[0] = r[0] * inv_n; out[1] = r[1] * inv_n; out[2] = r[2] * inv_n; out[3] = r[3] * inv_n; out[4] = r[4] * inv_tmp;
     }

@@ -48,8 +48,7 @@
 //             c_lap_b = w_lap (b == 0 ? 1 + Bp - B : 1) / (Bp Vg), each computed in double and rounded once
 //
 // Reduction tree of every sum (depth = the number of additions on the longest path, what the error bound counts):
-//   * workgroup: xor-butterfly over the 64 lanes of each wave (strides 32, 16, 8, 4, 2, 1: 6 levels; every lane holds the same bits), then
-//     wave 0 + wave 1 + wave 2 + wave 3 left to right (3 more);
+//   * workgroup: reduce.h's block_sum over the four waves (depth 9);
 //   * cross-entropy: finishing thread t adds the workgroup partials t, t + 256, ... in order, then the workgroup tree over the 256 threads:
 //     depth = 9 + (ceil(nwg / 256) - 1) + 9,  nwg = ceil(rows / 256);
 //   * garment: an item's ceil(Vg / 256) workgroup partials left to right by one finishing thread (item 0's Laplacian sum is then multiplied
@@ -57,30 +56,19 @@
 //     depth = 9 + (ceil(Vg / 256) - 1) + (ceil(B / 256) - 1) + 9  (+ 1 product for item 0's Laplacian weight);
 //   * PCA: depth = (ceil(B P / 256) - 1) + 9.
 //   The order depends on the shape alone: two runs give the same bits, with or without gradient buffers.
-#include "g4d_common.h"
+#include "reduce.h"
 
 namespace g4d {
 namespace {
 
 constexpr int kS1Block = 256;
 constexpr int kS1Terms = 4;   // L2, MSRE, penetration, Laplacian
-
-__device__ __forceinline__ float s1_block_sum(float v, float *sh) {   // the tree of refine_loss.hip's rl_block_sum
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = v + __shfl_xor(v, m, 64);
-    const int w = threadIdx.x >> 6;
-    __syncthreads();   // sh may still be read by the previous call
-    if ((threadIdx.x & 63) == 0) sh[w] = v;
-    __syncthreads();
-    return ((sh[0] + sh[1]) + sh[2]) + sh[3];
-}
-
-__device__ __forceinline__ float s1_norm3(float x, float y, float z) { return sqrtf((x * x + y * y) + z * z); }
+constexpr int kS1Waves = kS1Block / 64;
 
 // ---------------------------------------------------------------------------------------------------------------------- cross-entropy
 __global__ void __launch_bounds__(kS1Block) s1_ce_kernel(long long rows, int c, const float *__restrict__ logits, const long long *__restrict__ labels,
                                                          float scale, float *__restrict__ partials, float *__restrict__ grad) {
-    __shared__ float sh[4];
+    __shared__ float sh[kS1Waves];
     const long long r = (long long)blockIdx.x * kS1Block + threadIdx.x;
     float loss = 0.f;
     if (r < rows) {
@@ -97,15 +85,15 @@ __global__ void __launch_bounds__(kS1Block) s1_ce_kernel(long long rows, int c, 
             for (int k = 0; k < c; ++k) g[k] = ok ? scale * (expf(x[k] - m) / s - (k == y ? 1.f : 0.f)) : 0.f;
         }
     }
-    const float t = s1_block_sum(loss, sh);
+    const float t = block_sum<kS1Waves>(loss, sh);
     if (threadIdx.x == 0) partials[blockIdx.x] = t;
 }
 
 __global__ void __launch_bounds__(kS1Block) s1_ce_finish(long long nwg, const float *__restrict__ partials, float inv_rows, float *__restrict__ out) {
-    __shared__ float sh[4];
+    __shared__ float sh[kS1Waves];
     float acc = 0.f;
     for (long long k = threadIdx.x; k < nwg; k += kS1Block) acc = acc + partials[k];
-    const float t = s1_block_sum(acc, sh);
+    const float t = block_sum<kS1Waves>(acc, sh);
     if (threadIdx.x == 0) out[0] = t * inv_rows;
 }
 
@@ -126,7 +114,7 @@ __global__ void __launch_bounds__(kS1Block) s1_cot_kernel(long long total, int v
     const float abx = bx - ax, aby = by - ay, abz = bz - az;   // v2 - v1
     const float acx = cx - ax, acy = cy - ay, acz = cz - az;   // v3 - v1
     const float bcx = cx - bx, bcy = cy - by, bcz = cz - bz;   // v3 - v2
-    const float n = s1_norm3(aby * acz - abz * acy, abz * acx - abx * acz, abx * acy - aby * acx);
+    const float n = norm3(aby * acz - abz * acy, abz * acx - abx * acz, abx * acy - aby * acx);
     float h1 = 0.f, h2 = 0.f, h3 = 0.f;
     if (n > 0.f) {                                             // false for NaN as well
         const float d1 = (abx * acx + aby * acy) + abz * acz;              // (v2 - v1) . (v3 - v1)
@@ -164,7 +152,7 @@ struct S1Args {
 };
 
 __global__ void __launch_bounds__(kS1Block) s1_terms_kernel(S1Args a) {
-    __shared__ float sh[4];
+    __shared__ float sh[kS1Waves];
     const int b = blockIdx.x / a.nblk, blk = blockIdx.x - b * a.nblk;
     const int i = blk * kS1Block + threadIdx.x;
     float s_l2 = 0.f, s_ms = 0.f, s_pen = 0.f, s_lap = 0.f;
@@ -190,7 +178,7 @@ __global__ void __launch_bounds__(kS1Block) s1_terms_kernel(S1Args a) {
         float tx, ty, tz, lx, ly, lz;
         s1_lap_row(i, a.vg, a.nf, gb, a.h_target + hb, a.faces, a.rowptr, a.inc, tx, ty, tz);
         s1_lap_row(i, a.vg, a.nf, pb, a.h_pred + hb, a.faces, a.rowptr, a.inc, lx, ly, lz);
-        const float cn = s1_norm3(tx, ty, tz), n = s1_norm3(lx, ly, lz);
+        const float cn = norm3(tx, ty, tz), n = norm3(lx, ly, lz);
         s_lap = fabsf(n - cn);
         if (a.grad) {
             float ux = 0.f, uy = 0.f, uz = 0.f;
@@ -205,7 +193,7 @@ __global__ void __launch_bounds__(kS1Block) s1_terms_kernel(S1Args a) {
             a.grad[e + 2] = a.c_l2 * dz - m * nz;
         }
     }
-    const float r0 = s1_block_sum(s_l2, sh), r1 = s1_block_sum(s_ms, sh), r2 = s1_block_sum(s_pen, sh), r3 = s1_block_sum(s_lap, sh);
+    const float r0 = block_sum<kS1Waves>(s_l2, sh), r1 = block_sum<kS1Waves>(s_ms, sh), r2 = block_sum<kS1Waves>(s_pen, sh), r3 = block_sum<kS1Waves>(s_lap, sh);
     if (threadIdx.x == 0) {
         float *o = a.partials + (size_t)blockIdx.x * kS1Terms;
         o[0] = r0; o[1] = r1; o[2] = r2; o[3] = r3;
@@ -230,7 +218,7 @@ __global__ void __launch_bounds__(kS1Block) s1_lap_grad_kernel(long long total, 
 __global__ void __launch_bounds__(kS1Block) s1_finish_kernel(int b, int nblk, const float *__restrict__ partials, float item0_weight, float inv_n, float inv_lap,
                                                              long long npca, const float *__restrict__ coeff, const float *__restrict__ coeff_gt, float inv_pca,
                                                              float c_pca, float *__restrict__ grad_coeff, float *__restrict__ out) {
-    __shared__ float sh[4];
+    __shared__ float sh[kS1Waves];
     float acc[kS1Terms] = {0.f, 0.f, 0.f, 0.f};
     for (int it = threadIdx.x; it < b; it += kS1Block) {
         const float *pf = partials + (size_t)it * nblk * kS1Terms;
@@ -253,8 +241,8 @@ __global__ void __launch_bounds__(kS1Block) s1_finish_kernel(int b, int nblk, co
     }
     float r[kS1Terms];
 #pragma unroll
-    for (int c = 0; c < kS1Terms; ++c) r[c] = s1_block_sum(acc[c], sh);
-    const float rp = s1_block_sum(pca, sh);
+    for (int c = 0; c < kS1Terms; ++c) r[c] = block_sum<kS1Waves>(acc[c], sh);
+    const float rp = block_sum<kS1Waves>(pca, sh);
     if (threadIdx.x == 0) {
         out[0] = r[0] * inv_n; out[1] = r[1] * inv_n; out[2] = r[2] * inv_n; out[3] = r[3] * inv_lap; out[4] = rp * inv_pca;
     }

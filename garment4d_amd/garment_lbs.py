@@ -16,7 +16,8 @@ from . import _cache
 from . import _lib
 from . import grad_ops
 from . import lbs as L
-from .gcn import _to_csr, normalize
+from . import mesh_tables
+from .gcn import normalize
 from .knn import KNN, knn_points
 
 
@@ -66,17 +67,16 @@ def _smoothing_csr(adj_old, device):
     copies: neither belongs in a forward that may be running under hipGraph capture)."""
     def build():
         import scipy.sparse as sp
-        adj = sp.csr_matrix(normalize(adj_old) - sp.eye(adj_old.shape[0]))
-        max_row = int(np.diff(adj.indptr).max()) if adj.shape[0] else 0
-        return _to_csr(adj, device) + (max_row,), adj   # `adj` pinned: _to_csr caches by object identity
+        m = mesh_tables.sorted_csr(sp.csr_matrix(normalize(adj_old) - sp.eye(adj_old.shape[0])))
+        return mesh_tables.csr_tensors(m, device) + (m.shape[0], mesh_tables.longest_row(m))
 
-    return _cache.by_identity(_smooth_csr_cache, 8, (adj_old,), str(device), build)[0]
+    return _cache.by_identity(_smooth_csr_cache, 8, (adj_old,), str(device), build)
 
 
 def smooth_weights(nn_W, adj_old, coeff=0.1, iters=100, method=None):
     """100 Jacobi steps  W <- W + coeff * ((D^-1 A - I) . W)  over the garment mesh (:385-390).
     method "jacobi": the steps as written, one SpMM-axpy kernel each (ping-pong buffers).
-    method "fused" (default when the mesh fits: Vg <= 5104, <= 8 entries per adjacency row): all steps in ONE hand-written launch,
+    method "fused" (default when the mesh fits: mesh_tables.MAX_VG vertices, MAX_ROW entries per adjacency row): all steps in ONE hand-written launch,
     the weights of a (frame, 4-joint slab) resident in LDS (g4d_jacobi_smooth_f32) -- bit-identical to "jacobi".
     method "operator": the same linear map applied as one dense fp32 matrix product (see smoothing_operator; a LIBRARY GEMM,
     kept as a cross-check only); differs from the step-by-step result only by rounding.  G4D_SMOOTH overrides the default."""
@@ -87,7 +87,7 @@ def smooth_weights(nn_W, adj_old, coeff=0.1, iters=100, method=None):
     if method == "fused":
         rowptr, colidx, vals, n, max_row = _smoothing_csr(adj_old, nn_W.device)
         assert n == Vg
-        if Vg <= 5104 and max_row <= 8:
+        if Vg <= mesh_tables.MAX_VG and max_row <= mesh_tables.MAX_ROW:
             x = nn_W.contiguous()
             out = torch.empty_like(x)
             _lib.call("g4d_jacobi_smooth_f32", F_, Vg, J, int(iters), float(coeff), max_row, x.data_ptr(), rowptr.data_ptr(), colidx.data_ptr(),

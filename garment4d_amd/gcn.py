@@ -34,6 +34,7 @@ from torch.nn.parameter import Parameter
 from . import _cache
 from . import _lib
 from . import grad_ops
+from . import mesh_tables
 from .tuning import current as _T
 from .fused import PackedLayer, linear
 
@@ -83,40 +84,24 @@ def adjacency_from_faces(faces, num_verts):
     return normalize(adjacency_old_from_faces(faces, num_verts) + sp.eye(num_verts))
 
 
-def _scipy_csr(adj):
-    """torch sparse (COO/CSR) or scipy sparse -> scipy CSR with sorted column indices."""
-    if isinstance(adj, torch.Tensor):
-        a = adj.detach().cpu()
-        a = a.coalesce() if a.layout == torch.sparse_coo else a.to_sparse_coo().coalesce()
-        import scipy.sparse as sp
-        m = sp.coo_matrix((a.values().numpy(), (a.indices()[0].numpy(), a.indices()[1].numpy())), shape=tuple(a.shape)).tocsr()
-    else:
-        m = adj.tocsr()
-    m.sort_indices()
-    return m
-
-
-def _csr_tensors(m, device):
-    return (torch.from_numpy(m.indptr.astype(np.int32)).to(device), torch.from_numpy(m.indices.astype(np.int32)).to(device),
-            torch.from_numpy(m.data.astype(np.float32)).to(device), m.shape[0])
-
-
 def _to_csr(adj, device):
-    """torch sparse (COO/CSR) or scipy sparse -> (rowptr, colidx, vals) int32/float32 on `device`, cached per object."""
-    return _cache.by_identity(_csr_cache, 32, (adj,), str(device), lambda: _csr_tensors(_scipy_csr(adj), device))
+    """torch sparse (COO/CSR) or scipy sparse -> (rowptr, colidx, vals, n) int32/float32 on `device`, cached per object."""
+    def build():
+        m = mesh_tables.sorted_csr(adj)
+        return mesh_tables.csr_tensors(m, device) + (m.shape[0],)
+
+    return _cache.by_identity(_csr_cache, 32, (adj,), str(device), build)
 
 
 _csr_t_cache = {}
 
 
 def _to_csr_t(adj, device):
-    """The CSR of adj^T -- (rowptr, colidx, vals, n) like _to_csr, cached per adjacency object: row u lists the v with adj[v, u] != 0 in
-    ASCENDING v, which is the summation order of dS = adj^T G in g4d_spmm_rows_grad_f32 (a defined order: the gradient is reproducible)."""
+    """The CSR of adj^T -- (rowptr, colidx, vals, n) like _to_csr, cached per adjacency object: ascending v inside row u is the summation
+    order of dS = adj^T G in g4d_spmm_rows_grad_f32 (mesh_tables.transposed)."""
     def build():
-        mt = _scipy_csr(adj).T.tocsr()
-        mt.sum_duplicates()
-        mt.sort_indices()
-        return _csr_tensors(mt, device)
+        mt = mesh_tables.transposed(mesh_tables.sorted_csr(adj))
+        return mesh_tables.csr_tensors(mt, device) + (mt.shape[0],)
 
     return _cache.by_identity(_csr_t_cache, 32, (adj,), str(device), build)
 

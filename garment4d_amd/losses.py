@@ -12,6 +12,7 @@ import torch
 from . import _cache
 from . import _lib
 from . import fused
+from . import mesh_tables
 from . import mesh_utils
 
 _vf = {}
@@ -69,22 +70,12 @@ def laplacian_csr(lap_adj, device):
     garment_lbs._smoothing_csr): scipy work and seven host-to-device copies, which do not belong inside a hipGraph capture."""
     def build():
         assert not torch.cuda.is_current_stream_capturing(), "laplacian_csr: build the operator before the capture (call the loss once eagerly)"
-        import scipy.sparse as sp
-        if torch.is_tensor(lap_adj):
-            c = lap_adj.detach().coalesce() if lap_adj.is_sparse else lap_adj.detach().to_sparse().coalesce()
-            ij = c.indices().cpu().numpy()
-            L = sp.csr_matrix((c.values().float().cpu().numpy(), (ij[0], ij[1])), shape=tuple(c.shape))
-        else:
-            L = sp.csr_matrix(lap_adj).astype(np.float32)
+        L = mesh_tables.sorted_csr(lap_adj).astype(np.float32)
         assert L.shape[0] == L.shape[1], "the Laplacian is square"
         L.sum_duplicates()
-        L.sort_indices()
-        Lt = sp.csr_matrix(L.T)
-        Lt.sort_indices()
-        rowsum = np.asarray(L.astype(np.float64).sum(1)).reshape(-1).astype(np.float32)
-        dev = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a).astype(dt)).to(device)
-        return (dev(L.indptr, np.int32), dev(L.indices, np.int32), dev(L.data, np.float32), dev(rowsum, np.float32),
-                dev(Lt.indptr, np.int32), dev(Lt.indices, np.int32), dev(Lt.data, np.float32))
+        rowsum = np.asarray(L.astype(np.float64).sum(1)).reshape(-1)
+        return (mesh_tables.csr_tensors(L, device) + (mesh_tables.to_device(rowsum, np.float32, device),)
+                + mesh_tables.csr_tensors(mesh_tables.transposed(L), device))
 
     return _cache.by_identity(_lap_cache, 8, (lap_adj,), str(device), build)
 
@@ -246,12 +237,8 @@ def face_incidence(faces3, vg, device):
         f = faces3.detach().cpu().numpy() if torch.is_tensor(faces3) else np.asarray(faces3)
         f = np.ascontiguousarray(f.reshape(-1, 3).astype(np.int64))
         assert f.size == 0 or (f.min() >= 0 and f.max() < vg), "a face names a vertex outside the garment"
-        flat = f.reshape(-1)
-        order = np.argsort(flat, kind="stable")                     # entry = face * 3 + corner, ascending within a vertex
-        rowptr = np.zeros(vg + 1, np.int64)
-        np.cumsum(np.bincount(flat, minlength=vg), out=rowptr[1:])
-        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a).astype(np.int32)).to(device)
-        return dev(f), dev(rowptr), dev(order)
+        rowptr, corners = mesh_tables.vertex_corners(f, vg)        # entry = face * 3 + corner, ascending within a vertex
+        return tuple(mesh_tables.to_device(a, np.int32, device) for a in (f, rowptr, corners))
 
     return _cache.by_identity(_inc_cache, 8, (faces3,), (int(vg), str(device)), build)
 

@@ -9,7 +9,7 @@ psbody.mesh is third-party code that is not available to this project: include/g
 
 Everything is fp32 on the current torch stream; no atomics and no host round trip inside the calls, so a caller may capture them in a hipGraph
 -- AFTER one eager call, which builds the per-topology tables (face order, vertex -> face CSR, Laplacian) on the host and caches them by the
-identity of the `faces` / `adj_old` objects.  Outside the kernels' domain (Vg <= 5104, <= 8 entries per row of the operators) the calls raise
+identity of the `faces` / `adj_old` objects.  Outside the kernels' domain (mesh_tables.MAX_VG, MAX_ROW entries per row of the operators) the calls raise
 NotImplementedError: there is no fallback."""
 import collections
 
@@ -18,11 +18,10 @@ import torch
 
 from . import _cache
 from . import _lib
+from . import mesh_tables
 from . import tuning
 from .garment_lbs import _smoothing_csr
-
-MAX_VG = 5104      # the LDS-resident kernels' domain (g4d_jacobi_smooth_f32's)
-MAX_ROW = 8
+from .mesh_tables import MAX_ROW, MAX_VG      # the LDS-resident kernels' domain
 
 Nearest = collections.namedtuple("Nearest", "point dist2 face part normal")
 
@@ -80,14 +79,10 @@ def mesh_topology(faces, num_verts, device, template=None):
             raise ValueError(f"mesh_topology: face indices must lie in [0, {num_verts})")
         tpl = template.detach().cpu().numpy() if torch.is_tensor(template) else np.asarray(template)
         order = _morton_order(tpl.reshape(-1, 3)[f].mean(1))
-        vid = f.reshape(-1)
-        fid = np.repeat(np.arange(f.shape[0], dtype=np.int64), 3)
-        by_vertex = np.lexsort((fid, vid))
-        rowptr = np.zeros(num_verts + 1, dtype=np.int64)
-        rowptr[1:] = np.cumsum(np.bincount(vid, minlength=num_verts))
-        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a).astype(np.int32)).to(device)
+        rowptr, corners = mesh_tables.vertex_corners(f, num_verts)
+        dev = lambda a: mesh_tables.to_device(a, np.int32, device)
         return dict(nf=int(f.shape[0]), nv=int(num_verts), faces=dev(f), faces_sorted=dev(f[order]), face_ids=dev(order), vf_rowptr=dev(rowptr),
-                    vf_fid=dev(fid[by_vertex]))
+                    vf_fid=dev(corners // 3))
 
     return _cache.by_identity(_topology_cache, 16, (faces,), (int(num_verts), str(device)), build)
 
@@ -167,13 +162,10 @@ def depenetration_operator(adj_old, device):
         inv = np.where(s > 0, 1.0 / np.where(s > 0, s, 1.0), 0.0)
         L = sp.csr_matrix(sp.eye(A.shape[0]) - sp.diags(inv).dot(A))
         L.sum_duplicates()
-        L.sort_indices()
-        Lt = sp.csr_matrix(L.T)
-        Lt.sort_indices()
-        dev = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a).astype(dt)).to(device)
-        rows = lambda m: int(np.diff(m.indptr).max()) if m.shape[0] else 0
-        return (dev(L.indptr, np.int32), dev(L.indices, np.int32), dev(L.data, np.float32), dev(Lt.indptr, np.int32), dev(Lt.indices, np.int32),
-                dev(Lt.data, np.float32), int(L.shape[0]), rows(L), rows(Lt))
+        L = mesh_tables.sorted_csr(L)
+        Lt = mesh_tables.transposed(L)
+        return (mesh_tables.csr_tensors(L, device) + mesh_tables.csr_tensors(Lt, device)
+                + (int(L.shape[0]), mesh_tables.longest_row(L), mesh_tables.longest_row(Lt)))
 
     return _cache.by_identity(_operator_cache, 8, (adj_old,), str(device), build)
 

@@ -158,3 +158,18 @@ def test_incidence_lists_every_corner_once():
     for i in (0, 7, c["Vg"] - 1):
         ent = inc[rowptr[i]:rowptr[i + 1]]
         assert (faces.reshape(-1)[ent] == i).all() and (np.diff(ent) > 0).all()
+
+
+def test_vertex_corner_table_orders_faces_per_vertex_and_keeps_an_isolated_vertex():
+    """mesh_tables.vertex_corners serves the incidence above and postprocess.mesh_topology's vertex -> face CSR: its entries // 3 are the
+    faces of each vertex ascending (the lexsort by (vertex, face) the normals' summation order is defined by); a vertex no face names has
+    an empty row."""
+    from garment4d_amd import mesh_tables
+    c = TW.garment_case(3, 1, 13, 15)
+    f = np.asarray(c["faces"]).reshape(-1, 3).astype(np.int64)
+    nv = c["Vg"] + 1                                     # one vertex more than the faces name
+    rowptr, corners = mesh_tables.vertex_corners(f, nv)
+    vid, fid = f.reshape(-1), np.repeat(np.arange(len(f)), 3)
+    by_vertex = np.lexsort((fid, vid))
+    assert np.array_equal(corners // 3, fid[by_vertex]) and np.array_equal(vid[corners], vid[by_vertex])
+    assert np.array_equal(rowptr[1:], np.cumsum(np.bincount(vid, minlength=nv))) and rowptr[0] == 0 and rowptr[-1] == rowptr[-2] == f.size
