@@ -3,215 +3,142 @@
 The library is built in-tree (garment4d_amd/lib/libg4d_hip.so) by `__graft_entry__.build()` /
 `make -C garment4d_amd/csrc`.  There is NO fallback: if the library is missing, or a call fails,
 this raises -- the product path never silently routes to PyTorch eager or to the CPU oracle.
+
+Nothing of the ABI is typed here by hand: every prototype's argtypes and restype, the fields of `g4d_mlp_args` and the `G4D_*` constants
+are read from include/g4d.h when the library is loaded (`parse_header`), and tests/abi_snapshot.txt is the reviewed record of what that
+gives -- a changed or new entry point shows up there as a changed or new line.
 """
 import ctypes
 import os
+import re
+import sys
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("G4D_LIB_PATH") or os.path.join(_HERE, "lib", "libg4d_hip.so")
-
-_vp = ctypes.c_void_p
-_I = ctypes.c_int
-_F = ctypes.c_float
-_LL = ctypes.c_longlong
-
-# name -> argtypes (stream last); every function returns int status (0 = ok)
-SIGNATURES = {
-    "g4d_fps_f32": [_I, _I, _I, _vp, _vp, _vp, _vp],
-    "g4d_fps_gather_f32": [_I, _I, _I, _vp, _vp, _vp, _vp, _vp],
-    "g4d_gather_f32": [_I, _I, _I, _I, _vp, _vp, _vp, _vp],
-    "g4d_gather_grad_f32": [_I, _I, _I, _I, _vp, _vp, _vp, _vp],
-    "g4d_ball_query_f32": [_I, _I, _I, _F, _I, _vp, _vp, _vp, _vp],
-    "g4d_ball_query_msg_f32": [_I, _I, _I, _I, _vp, _vp, _vp, _vp, _vp, _vp],
-    "g4d_ball_query_boxes_f32": [_I, _I, _I, _I, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "g4d_ball_query_lanes_f32": [_I, _I, _I, _I, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "g4d_ball_query_lanes_qsort_bytes": [_I, _I],
-    "g4d_ball_grid_bytes": [_I, _I],
-    "g4d_ball_grid_build_f32": [_I, _I, _F, _vp, _vp, _vp],
-    "g4d_ball_grid_query_f32": [_I, _I, _I, _I, _vp, _vp, _vp, _vp, _vp, _vp, _F, _vp],
-    "g4d_ball_query_grid_f32": [_I, _I, _I, _I, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "g4d_group_f32": [_I, _I, _I, _I, _I, _vp, _vp, _vp, _vp],
-    "g4d_group_grad_f32": [_I, _I, _I, _I, _I, _vp, _vp, _vp, _vp],
-    "g4d_three_nn_f32": [_I, _I, _I, _vp, _vp, _vp, _vp, _vp],
-    "g4d_three_nn_grid_f32": [_I, _I, _I, _vp, _vp, _vp, _vp, _vp, _vp],
-    "g4d_three_interp_f32": [_I, _I, _I, _I, _vp, _vp, _vp, _vp, _vp],
-    "g4d_three_interp_grad_f32": [_I, _I, _I, _I, _vp, _vp, _vp, _vp, _vp],
-    "g4d_linear_f32": [_LL, _I, _I, _I, _vp, _I, _vp, _vp, _vp, _I, _I, _I, _vp, _I, _I, _vp],
-    "g4d_group_linear_f32": [_I, _I, _I, _I, _I, _I, _vp, _vp, _vp, _vp, _I, _I, _vp, _vp, _vp, _I, _I, _vp, _I, _I, _vp],
-    "g4d_interp_linear_f32": [_I, _I, _I, _I, _I, _vp, _vp, _vp, _vp, _I, _I, _vp, _vp, _vp, _I, _vp, _I, _I, _vp],
-    "g4d_gcn_linear_f32": [_I, _I, _I, _vp, _I, _vp, _vp, _vp, _I, _I, _vp, _vp, _vp, _I, _vp, _I, _I, _vp],
-    "g4d_mlp_stack_f32": [_I, _LL, _I, _vp, _I, _I, _I, _I, _I, _I, _vp, _vp, _vp, _vp, _I, _I, _I, _I, _vp, _vp, _vp, _vp,
-                          _I, _vp, _vp, _vp, _I, _vp, _vp, _vp, _vp, _vp, _vp, _I, _vp, _I, _I, _I, _vp, _I, _vp],
-    "g4d_mlp_stack_bf16": [_I, _LL, _I, _vp, _I, _I, _I, _I, _I, _I, _vp, _vp, _vp, _vp, _I, _I, _I, _I, _vp, _vp, _vp, _vp,
-                           _I, _vp, _vp, _vp, _I, _vp, _vp, _vp, _vp, _vp, _vp, _I, _vp, _I, _I, _I, _vp, _I, _vp],
-    "g4d_mlp_wave_f32": [_I, _LL, _I, _vp, _I, _I, _I, _I, _I, _I, _vp, _vp, _vp, _vp, _I, _I, _I, _I, _vp, _vp, _vp, _vp,
-                         _I, _vp, _vp, _vp, _I, _vp, _vp, _vp, _vp, _vp, _vp, _I, _vp, _I, _I, _vp],
-    "g4d_pool_rows_f32": [_I, _I, _I, _vp, _I, _vp, _I, _I, _I, _vp],
-    "g4d_bn_slice_rows": [_LL, _I],
-    "g4d_bn_stats_ws_bytes": [_LL, _I],
-    "g4d_bn_stats_f32": [_LL, _I, _vp, _I, _vp, _vp, _vp, _vp],
-    "g4d_bn_act_f32": [_LL, _I, _vp, _I, _vp, _vp, _F, _vp, _vp, _I, _vp, _I, _vp],
-    "g4d_bn_act_grad_reduce_ws_bytes": [_LL, _I],
-    "g4d_bn_act_grad_reduce_f32": [_LL, _I, _vp, _I, _vp, _I, _vp, _vp, _F, _vp, _vp, _I, _vp, _vp, _vp, _vp],
-    "g4d_bn_act_grad_f32": [_LL, _I, _vp, _I, _vp, _I, _vp, _vp, _F, _vp, _vp, _I, _I, _vp, _vp, _vp, _I, _vp],
-    "g4d_pool_rows_max_grad_f32": [_I, _I, _I, _vp, _I, _vp, _I, _I, _vp, _vp],
-    "g4d_transpose_f32": [_I, _I, _I, _vp, _vp, _vp],
-    "g4d_copy_segments_f32": [_I, _vp, _vp, _vp, _vp],
-    "g4d_linear_interp_add_f32": [_LL, _I, _I, _I, _I, _I, _vp, _I, _vp, _vp, _I, _vp, _vp, _vp, _vp, _I, _vp, _I, _I, _vp],
-    "g4d_tuning_set": [ctypes.c_char_p, _LL],
-    "g4d_tuning_set_thread": [ctypes.c_char_p, ctypes.c_longlong, _I],
-    "g4d_interp_concat_f32": [_I, _I, _I, _I, _I, _vp, _vp, _vp, _vp, _vp, _vp],
-    "g4d_spmm_rows_f32": [_I, _I, _I, _vp, _vp, _vp, _vp, _vp, _I, _vp, _vp],
-    "g4d_spmm_rows_grad_f32": [_I, _I, _I, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "g4d_col_sum_rows_ws_bytes": [_LL, _I],
-    "g4d_col_sum_rows_f32": [_LL, _I, _vp, _vp, _vp, _vp, _vp],
-    "g4d_gemm_tn_slice_rows": [_LL, _I, _I],
-    "g4d_gemm_tn_ws_bytes": [_LL, _I, _I],
-    "g4d_gemm_tn_f32": [_LL, _I, _I, _I, _vp, _vp, _vp, _vp, _vp],
-    "g4d_gcn_agg_linear_f32": [_I, _I, _I, _vp, _vp, _vp, _vp, _vp, _I, _vp, _vp, _I, _vp, _vp],
-    "g4d_gcn_agg_linear_meta_f32": [_I, _I, _I, _vp, _vp, _vp, _vp, _vp, _I, _vp, _vp, _I, _vp, _vp, _vp],
-    "g4d_gcn_tile_meta_bytes": [_I],
-    "g4d_gcn_tile_meta_build": [_I, _vp, _vp, _vp, _vp, _vp],
-    "g4d_knn_f32": [_I, _I, _I, _I, _vp, _vp, _vp, _vp, _vp],
-    "g4d_knn_blend_weights_f32": [_I, _I, _I, _I, _I, _I, _vp, _vp, _vp, _vp, _vp],
-    "g4d_mgn_skin_f32": [_I, _I, _I, _I, _I, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "g4d_mgn_skin_grad_f32": [_I, _I, _I, _I, _I, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "g4d_pos_encode_f32": [_I, _I, _I, _I, _I, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _I, _I, _vp],
-    "g4d_temporal_attention_scratch_floats": [_I, _I, _I],
-    "g4d_temporal_attention_f32": [_I, _I, _I, _I, _vp, _vp, _vp, _vp, _I, _I, _vp],
-    "g4d_pos_encode_grad_ws_bytes": [_I, _I, _I],
-    "g4d_pos_encode_grad_f32": [_I, _I, _I, _I, _I, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _I, _I, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "g4d_temporal_attention_grad_scratch_floats": [_I, _I, _I],
-    "g4d_temporal_attention_grad_f32": [_I, _I, _I, _I, _vp, _vp, _vp, _I, _I, _vp, _vp, _vp],
-    "g4d_interpenetration_f32": [_I, _I, _I, _vp, _vp, _vp, _vp, _I, _vp, _vp],
-    "g4d_refine_loss_ws_bytes": [_I, _I, _I],
-    "g4d_refine_loss_f32": [_I, _I, _I, _I, _vp, _vp, _vp, _vp, _vp, _I, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _F, _F, _F, _F, _I, _vp, _vp, _vp, _vp, _vp],
-    "g4d_stage1_loss_ws_bytes": [_LL, _I, _I, _I, _I],
-    "g4d_stage1_ce_f32": [_LL, _I, _vp, _vp, _F, _vp, _vp, _vp, _vp],
-    "g4d_stage1_garment_f32": [_I, _I, _I, _I, _I, _I, _vp, _vp, _vp, _vp, _vp, _vp, _I, _vp, _vp, _vp, _vp, _vp, _F, _F, _F, _F, _vp, _vp, _vp, _vp, _vp],
-    "g4d_mlp_chain_supported": [_I, _vp],
-    "g4d_sa_xyz_mlp3_supported": [_I, _I, _I, _I],
-    "g4d_sa_xyz_mlp3_f32": [_I, _I, _I, _I, _vp, _vp, _vp, _I, _I, _I, _vp, _I, _vp, _vp, _vp, _I, _vp, _vp, _vp, _I, _vp, _vp, _I, _vp, _I, _I, _vp],
-    "g4d_mlp_chain_f32": [_I, _LL, _I, _vp, _I, _I, _I, _I, _I, _I, _vp, _vp, _vp, _vp, _I, _I, _I, _I, _vp, _vp, _vp, _vp, _I, _vp, _vp, _vp,
-                          _vp, _vp, _vp, _I, _vp, _I, _I, _I, _vp, _I, _vp],
-    "g4d_mlp_chain_bf16": [_I, _LL, _I, _vp, _I, _I, _I, _I, _I, _I, _vp, _vp, _vp, _vp, _I, _I, _I, _I, _vp, _vp, _vp, _vp, _I, _vp, _vp, _vp,
-                           _vp, _vp, _vp, _I, _vp, _I, _I, _I, _vp, _I, _vp],
-    "g4d_frag_bf16_elems": [_LL, _I],
-    "g4d_interp_concat_frag_bf16": [_I, _I, _I, _I, _I, _vp, _vp, _vp, _vp, _I, _vp, _vp],
-    "g4d_gemm_frag_bf16": [_LL, _I, _vp, _vp, _vp, _vp, _I, _I, _vp, _I, _vp, _I, _I, _vp],
-    "g4d_mlp_chain_cells_bf16": [_I, _LL, _I, _vp, _I, _I, _I, _I, _I, _I, _vp, _vp, _vp, _vp, _I, _I, _I, _I, _vp, _vp, _vp, _vp, _I, _vp, _vp, _vp,
-                                 _vp, _vp, _vp, _I, _vp, _I, _I, _I, _vp, _I, _vp, _vp],
-    "g4d_mlp_chain_bf16x3": [_I, _LL, _I, _vp, _I, _I, _I, _I, _I, _I, _vp, _vp, _vp, _vp, _I, _I, _I, _I, _vp, _vp, _vp, _vp, _I, _vp, _vp, _vp,
-                           _vp, _vp, _vp, _I, _vp, _I, _I, _I, _vp, _I, _vp],
-    "g4d_mlp_chain_table_f32": [ctypes.c_longlong, _I, _I, _I, _vp, _vp, _vp, _vp, _vp, _vp, _I, _I, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _I, _I, _I, _vp, _I, _vp],
-    "g4d_mlp_chain_group_table_f32": [ctypes.c_longlong, _I, _I, _I, _vp, _vp, _vp, _vp, _I, _I, _vp, _vp, _vp, _I, _vp, _vp, _vp, _vp, _vp, _vp, _I, _vp, _I, _I, _vp],
-    "g4d_mlp_args_size": [],
-    "g4d_mlp_run": [_I, _vp, _vp],
-    "g4d_sa_table_supported": [ctypes.c_longlong, _I, _I, _I],
-    "g4d_sa_table_ws_bytes": [ctypes.c_longlong, _I, _I, _I],
-    "g4d_mlp_chain_group_table_ws_f32": [ctypes.c_longlong, _I, _I, _I, _vp, _vp, _vp, _vp, _I, _I, _vp, _vp, _vp, _I, _vp, _vp, _vp, _vp, _vp, _vp, _I, _vp, _I, _I, _vp,
-                                         ctypes.c_longlong, _vp],
-    "g4d_three_nn_cells_f32": [_I, _I, _I, _vp, _vp, _vp, _vp, _vp, _vp],
-    "g4d_mlp_chain_interp_init_f32": [ctypes.c_longlong, _I, _I, _I, _vp, _vp, _I, _vp, _vp, _I, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _I, _I, _I, _vp, _I, _vp],
-    "g4d_three_nn_multi_f32": [_I, _I, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "g4d_ball_query_msg2_f32": [_I, _I, _I, _I, _vp, _vp, _vp, _vp, _vp, _I, _I, _vp, _vp, _vp, _vp, _vp, _vp],
-    "g4d_fps_gather_pair_supported": [_I, _I, _I],
-    "g4d_fps_gather_pair_f32": [_I, _I, _I, _I, _vp, _vp, _vp, _vp, _vp, _vp],
-    "g4d_sa_xyz_mlp3_pair_f32": [_I, _I, _I, _vp, _vp, _I, _vp, _I, _I, _vp, _vp, _I, _vp, _vp, _vp, _I, _vp, _vp, _vp, _I, _vp, _vp, _I, _I, _vp, _vp, _I, _vp, _vp, _vp, _I, _vp, _vp, _vp, _I, _vp, _vp, _I, _vp],
-    "g4d_fps_gather_grid_f32": [_I, _I, _I, _vp, _vp, _vp, ctypes.c_float, _vp, _vp],
-    "g4d_three_nn_cells_sorted_f32": [_I, _I, _I, _vp, _vp, _vp, _vp, _vp],
-    "g4d_three_nn_pruned_supported": [_I, _I],
-    "g4d_three_nn_pruned_ws_bytes": [_I],
-    "g4d_three_nn_pruned_f32": [_I, _I, _I, _vp, _vp, _vp, _vp, _vp, _I, _vp, ctypes.c_longlong, _vp],
-    "g4d_mlp_chain_table_cells_f32": [ctypes.c_longlong, _I, _I, _I, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _I, _I, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _I, _I, _I, _vp, _I, _vp],
-    "g4d_search_multi_f32": [_I, _I, _I, _I, _vp, _vp, _vp, _vp, _vp, _I, _I, _vp, _vp, _vp, _vp, _vp, _I, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "g4d_launch_group_begin": [],
-    "g4d_launch_group_end": [_vp, _vp],
-    "g4d_launch_group_abort": [],
-    "g4d_lbs_one_supported": [_I, _I],
-    "g4d_lbs_one_f32": [_I, _I, _I, _I, _I, _vp, _I, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "g4d_lbs_mfma_supported": [_I, _I],
-    "g4d_lbs_mfma_ws_bytes": [_I, _I],
-    "g4d_lbs_mfma_f32": [_I, _I, _I, _I, _I, _vp, _I, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_longlong, _vp],
-    "g4d_lbs_fused_f32": [_I, _I, _I, _I, _I, _vp, _I, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "g4d_segment_select_f32": [_I, _I, _I, _I, _I, _vp, _vp, _vp, _vp],
-    "g4d_segment_take_f32": [_I, _I, _I, _I, _vp, _vp, _vp, _vp],
-    "g4d_vertex_normals_f32": [_I, _I, _vp, _vp, _vp, _vp, _vp, _vp],
-    "g4d_spmm_axpy_rows_f32": [_I, _I, _I, _vp, _vp, _vp, _vp, _F, _vp, _vp],
-    "g4d_jacobi_smooth_f32": [_I, _I, _I, _I, _F, _I, _vp, _vp, _vp, _vp, _vp, _vp],
-    "g4d_gather_rows_f32": [_I, _I, _I, _I, _vp, _vp, _vp, _vp],
-    "g4d_lbs_shape_f32": [_I, _I, _I, _vp, _I, _vp, _vp, _vp, _vp],
-    "g4d_joint_regress_f32": [_I, _I, _I, _vp, _I, _vp, _vp, _vp],
-    "g4d_rodrigues_f32": [_I, _vp, _vp, _vp],
-    "g4d_rigid_transform_f32": [_I, _I, _I, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "g4d_lbs_pose_skin_f32": [_I, _I, _I, _I, _vp, _vp, _vp, _vp, _I, _vp, _vp, _vp, _vp],
-    "g4d_taubin_smooth_f32": [_I, _I, _I, _I, _F, _F, _I, _vp, _vp, _vp, _vp, _vp, _vp],
-    "g4d_vertex_normals_area_f32": [_I, _I, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "g4d_mesh_aabb_f32": [_I, _I, _I, _vp, _vp, _vp, _vp],
-    "g4d_mesh_nearest_f32": [_I, _I, _I, _I, _I, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "g4d_depen_targets_f32": [_I, _I, _F, _F, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "g4d_depen_solve_f32": [_I, _I, _I, _I, _I, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-}
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "g4d.h")
 
 _lib = None
-
-
-RESTYPES = {"g4d_mlp_args_size": ctypes.c_uint, "g4d_bn_slice_rows": ctypes.c_longlong, "g4d_bn_stats_ws_bytes": ctypes.c_longlong, "g4d_bn_act_grad_reduce_ws_bytes": ctypes.c_longlong, "g4d_col_sum_rows_ws_bytes": ctypes.c_longlong, "g4d_gemm_tn_slice_rows": ctypes.c_longlong, "g4d_gemm_tn_ws_bytes": ctypes.c_longlong, "g4d_sa_table_ws_bytes": ctypes.c_longlong, "g4d_gcn_tile_meta_bytes": ctypes.c_longlong, "g4d_frag_bf16_elems": ctypes.c_longlong, "g4d_lbs_mfma_ws_bytes": ctypes.c_longlong, "g4d_three_nn_pruned_ws_bytes": ctypes.c_longlong, "g4d_temporal_attention_scratch_floats": ctypes.c_size_t, "g4d_temporal_attention_grad_scratch_floats": ctypes.c_size_t, "g4d_pos_encode_grad_ws_bytes": ctypes.c_longlong, "g4d_refine_loss_ws_bytes": ctypes.c_longlong, "g4d_stage1_loss_ws_bytes": ctypes.c_longlong, "g4d_ball_grid_bytes": ctypes.c_size_t, "g4d_ball_query_lanes_qsort_bytes": ctypes.c_size_t}   # everything else returns an int status
+_header = None   # HEADER_PATH once the names below are bound from it
 
 
 class G4DError(RuntimeError):
     pass
 
 
-MLP_ARGS_VERSION = 1
-MLP_STACK_F32, MLP_STACK_BF16, MLP_WAVE_F32, MLP_CHAIN_F32, MLP_CHAIN_BF16, MLP_CHAIN_BF16X3 = range(6)   # enum g4d_mlp_family
+_SCALARS = {"int": ctypes.c_int, "float": ctypes.c_float, "long long": ctypes.c_longlong, "size_t": ctypes.c_size_t, "unsigned": ctypes.c_uint}
 
 
-class MlpArgs(ctypes.Structure):
-    """include/g4d.h `g4d_mlp_args`, field for field -- the ONE argument block of the whole-stack launchers (g4d_mlp_run).  tests/test_abi_cpu.py
-    checks sizeof against the library's g4d_mlp_args_size() and the field order against the header's text."""
-    _fields_ = [("size", ctypes.c_uint), ("version", ctypes.c_uint), ("mode", _I), ("K0", _I), ("rows", ctypes.c_longlong),
-                ("X", _vp), ("ldx", _I),
-                ("N", _I), ("P", _I), ("S", _I), ("C", _I), ("use_xyz", _I), ("xyz", _vp), ("new_xyz", _vp), ("feats", _vp), ("idx", _vp),
-                ("n", _I), ("m", _I), ("C2", _I), ("C1", _I), ("known_feats", _vp), ("skip", _vp), ("dist2", _vp), ("nn_idx", _vp),
-                ("Vg", _I), ("rowptr", _vp), ("colidx", _vp), ("vals", _vp),
-                ("nlayers", _I), ("W", _vp), ("scale", _vp), ("shift", _vp), ("Kpad", _vp), ("Cout", _vp), ("relu", _vp),
-                ("pool", _I), ("out", _vp), ("ldo", _I), ("col0", _I), ("tap_layer", _I), ("tap_out", _vp), ("tap_ld", _I), ("unknown_grid", _vp)]
+def _ctype(decl, where, named=True):
+    """The ctypes type of one C declaration of include/g4d.h (`const float *const *scale`, `long long rows`, a return type with
+    named=False): any pointer and g4d_stream_t -> c_void_p, `const char *` -> c_char_p, the scalars of _SCALARS; anything else raises."""
+    base, star, rest = decl.partition("*")
+    words = [w for w in base.split() if w != "const"]
+    if named and not star:
+        words.pop()   # the parameter's / field's own name
+    base = " ".join(words)
+    if star:
+        return ctypes.c_char_p if base == "char" and "*" not in rest else ctypes.c_void_p
+    if base == "g4d_stream_t":
+        return ctypes.c_void_p
+    if base not in _SCALARS:
+        raise G4DError(f"include/g4d.h: {where}: no ctypes type known for `{' '.join(decl.split())}`")
+    return _SCALARS[base]
 
-    def __init__(self, **kw):
-        super().__init__(size=ctypes.sizeof(MlpArgs), version=MLP_ARGS_VERSION, tap_layer=-1, **kw)
+
+def parse_header(text):
+    """include/g4d.h -> ({entry point: (restype, [argtypes])}, [(field, type)] of g4d_mlp_args, {G4D_* #define or enumerator: int}).
+    Reads that header and nothing else: comments and preprocessor lines are dropped, the rest is cut into statements at ; { }."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    consts = {n: int(v, 0) for n, v in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(G4D_\w+)[ \t]+(-?(?:0[xX][0-9a-fA-F]+|\d+))[ \t]*$", text, flags=re.M)}
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    for body in re.findall(r"\benum\s+\w+\s*\{(.*?)\}", text, flags=re.S):
+        consts.update((n, int(v, 0)) for n, v in re.findall(r"(G4D_\w+)\s*=\s*(-?\w+)", body))
+    fields = []
+    struct = re.search(r"\bstruct\s+g4d_mlp_args\s*\{(.*?)\}", text, flags=re.S)
+    for decl in filter(str.strip, struct.group(1).split(";") if struct else ()):
+        first, *more = decl.split(",")
+        base = first.partition("*")[0] if "*" in first else first.rsplit(None, 1)[0]   # `const float *a, *const *b, c`: the type without the first name
+        for piece in [first] + [base + " " + p for p in more]:
+            fields.append((re.findall(r"\w+", piece)[-1], _ctype(piece, "g4d_mlp_args")))
+    protos = {}
+    for stmt in re.split(r"[;{}]", text):
+        if "(" not in stmt:
+            continue
+        m = re.fullmatch(r"\s*([\w\s*]+?)\b(g4d_\w+)\s*\(([^()]*)\)\s*", stmt)
+        if not m:
+            raise G4DError(f"include/g4d.h: cannot read `{' '.join(stmt.split())}` as a prototype")
+        ret, name, params = m.groups()
+        params = [] if params.strip() in ("void", "") else params.split(",")
+        protos[name] = (_ctype(ret, name, named=False), [_ctype(p, name) for p in params])
+    return protos, fields, consts
+
+
+# what call() shows a g4d_mlp_run as in traces and timing tables: the positional entry point of the family, keyed by the header's enumerator
+_MLP_FAMILY_LABELS = {"G4D_MLP_STACK_F32": "g4d_mlp_stack_f32", "G4D_MLP_STACK_BF16": "g4d_mlp_stack_bf16", "G4D_MLP_WAVE_F32": "g4d_mlp_wave_f32",
+                      "G4D_MLP_CHAIN_F32": "g4d_mlp_chain_f32", "G4D_MLP_CHAIN_BF16": "g4d_mlp_chain_bf16", "G4D_MLP_CHAIN_BF16X3": "g4d_mlp_chain_bf16x3"}
+
+
+def _bind_header():
+    """Read include/g4d.h and define the module's derived names from it: PROTOTYPES (name -> (restype, argtypes)), SIGNATURES (name ->
+    argtypes), RESTYPES (name -> restype where it is not c_int), CONSTANTS (every integer G4D_* #define and enumerator), MLP_ARGS_VERSION,
+    MLP_STACK_F32 ... MLP_CHAIN_BF16X3 (enum g4d_mlp_family) and MlpArgs."""
+    global _header
+    try:
+        with open(HEADER_PATH) as f:
+            protos, fields, consts = parse_header(f.read())
+    except OSError as e:
+        raise G4DError(f"{HEADER_PATH} cannot be read ({e.strerror}): the ctypes binding is derived from it. There is no fallback table.")
+
+    class MlpArgs(ctypes.Structure):
+        """include/g4d.h `g4d_mlp_args`, read from the header -- the ONE argument block of the whole-stack launchers (g4d_mlp_run).
+        tests/test_abi_cpu.py checks sizeof against the library's g4d_mlp_args_size() and the fields against tests/abi_snapshot.txt."""
+        _fields_ = fields
+
+        def __init__(self, **kw):
+            super().__init__(size=ctypes.sizeof(MlpArgs), version=consts["G4D_MLP_ARGS_VERSION"], tap_layer=-1, **kw)
+
+    globals().update(
+        PROTOTYPES=protos, SIGNATURES={n: a for n, (r, a) in protos.items()}, RESTYPES={n: r for n, (r, a) in protos.items() if r is not ctypes.c_int},
+        CONSTANTS=consts, MlpArgs=MlpArgs, _MLP_FAMILY_NAMES={consts[k]: v for k, v in _MLP_FAMILY_LABELS.items()},
+        **{k[4:]: v for k, v in consts.items() if k.startswith("G4D_MLP_")})   # MLP_ARGS_VERSION and the families
+    _header = HEADER_PATH
+
+
+def __getattr__(name):
+    # the derived names, for code that reads them before lib() has loaded the library (numerics.MODES, tests of the tables)
+    if _header is None and not name.startswith("__"):
+        _bind_header()
+        if name in globals():
+            return globals()[name]
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 def lib():
-    """Load libg4d_hip.so once; raise (loudly) when it is absent."""
+    """Load libg4d_hip.so once, typed as include/g4d.h declares it; raise (loudly) when either is absent."""
     global _lib
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise G4DError(
                 f"{LIB_PATH} not found: the HIP extension is not built. Run `python -c 'import "
                 f"__graft_entry__ as g; g.build()'` (or `make -C garment4d_amd/csrc`). There is no fallback path.")
+        if _header is None:
+            _bind_header()
         # torch first: its wheel bundles a libamdhip64; loading ours before it would bring in /opt/rocm's copy as a SECOND HIP runtime
         # in the process, and the library's launches would then run in a runtime that never saw torch's device / streams
         # ("no ROCm-capable device is detected" from the first hipFuncSetAttribute)
         import torch  # noqa: F401
         L = ctypes.CDLL(LIB_PATH)
-        for name, args in SIGNATURES.items():
+        for name, (restype, argtypes) in PROTOTYPES.items():
             fn = getattr(L, name)  # AttributeError if the library does not export a declared symbol
-            fn.argtypes = args
-            fn.restype = RESTYPES.get(name, _I)
-        L.g4d_version.restype = _I
-        L.g4d_get_distance_contraction.restype = _I
-        L.g4d_set_distance_contraction.argtypes = [_I]
-        L.g4d_set_distance_contraction.restype = _I
-        L.g4d_set_distance_contraction_thread.argtypes = [_I]
-        L.g4d_set_distance_contraction_thread.restype = _I
-        L.g4d_last_error.restype = ctypes.c_char_p
+            fn.argtypes = argtypes
+            fn.restype = restype
         _lib = L
     return _lib
 
 
 _TRACE = os.environ.get("G4D_TRACE_CALLS", "0") != "0"   # debugging: every C-ABI call with its integer / float arguments on stderr
 _TIMED = None   # measurement: a list collecting (name, integer args, start event, end event) of every call (timed_calls)
+_UNTIMED = ("g4d_tuning_set", "g4d_tuning_set_thread", "g4d_launch_group_begin")   # host state only: nothing to put events around
 
 
 class timed_calls:
@@ -236,41 +163,29 @@ class timed_calls:
         return [(name, ints, e0.elapsed_time(e1) * 1e3) for name, ints, e0, e1 in self._rec]
 
 
-_MLP_FAMILY_NAMES = ("g4d_mlp_stack_f32", "g4d_mlp_stack_bf16", "g4d_mlp_wave_f32", "g4d_mlp_chain_f32", "g4d_mlp_chain_bf16", "g4d_mlp_chain_bf16x3")
-
-
 def call(name, *args):
     """Invoke a C-ABI entry point; non-zero status -> G4DError (the reference would exit(-1))."""
     L = lib()
-    if name == "g4d_mlp_run" and (_TRACE or _TIMED is not None):
-        # tracing / timing tables name the kernel family behind the argument block and list its leading integers (mode, rows, K0, ...) as the
-        # positional entry points did
-        blk = args[1].contents if hasattr(args[1], "contents") else MlpArgs.from_address(args[1])
-        fam = _MLP_FAMILY_NAMES[args[0]] if blk.unknown_grid is None else "g4d_mlp_chain_cells_bf16"
-        shown = (blk.mode, blk.rows, blk.K0, blk.ldx, blk.N, blk.P, blk.S, blk.C, blk.use_xyz, blk.n, blk.m, blk.C2, blk.C1, blk.nlayers, blk.pool)
+    timed = _TIMED is not None and args and name not in _UNTIMED
+    if _TRACE or timed:
+        label, shown = name, tuple(a for a in args if isinstance(a, int) and not isinstance(a, bool) and abs(a) < (1 << 31))
+        if name == "g4d_mlp_run":
+            # tracing / timing tables name the kernel family behind the argument block and list its leading integers (mode, rows, K0, ...)
+            # as the positional entry points did
+            blk = args[1].contents if hasattr(args[1], "contents") else MlpArgs.from_address(args[1])
+            label = _MLP_FAMILY_NAMES[args[0]] if blk.unknown_grid is None else "g4d_mlp_chain_cells_bf16"
+            shown = (blk.mode, blk.rows, blk.K0, blk.ldx, blk.N, blk.P, blk.S, blk.C, blk.use_xyz, blk.n, blk.m, blk.C2, blk.C1, blk.nlayers, blk.pool)
+            if _TRACE:
+                print("g4d call g4d_mlp_run ->", label, *shown, file=sys.stderr)
         if _TRACE:
-            import sys
-            print("g4d call g4d_mlp_run ->", fam, *shown, file=sys.stderr)
-        if _TIMED is not None:
-            import torch
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            rc = L.g4d_mlp_run(*args)
-            e1.record()
-            _TIMED.append((fam, shown, e0, e1))
-            if rc != 0:
-                raise G4DError(f"g4d_mlp_run({fam}) failed with status {rc}: {L.g4d_last_error().decode(errors='replace')}")
-            return rc
-    if _TRACE:
-        import sys
-        print("g4d call", name, *[a for a in args if isinstance(a, (int, float)) and abs(a) < (1 << 31)], file=sys.stderr)
-    if _TIMED is not None and args and name not in ("g4d_tuning_set", "g4d_tuning_set_thread", "g4d_launch_group_begin"):
+            print("g4d call", name, *[a for a in args if isinstance(a, (int, float)) and abs(a) < (1 << 31)], file=sys.stderr)
+    if timed:
         import torch
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         rc = getattr(L, name)(*args)
         e1.record()
-        _TIMED.append((name, tuple(a for a in args if isinstance(a, int) and not isinstance(a, bool) and abs(a) < (1 << 31)), e0, e1))
+        _TIMED.append((label, shown, e0, e1))
     else:
         rc = getattr(L, name)(*args)
     if rc != 0:
@@ -281,6 +196,13 @@ def call(name, *args):
 def host_array(ctype, values):
     """`values` as a host array of `ctype`, in the form the C ABI takes it: a void pointer -- which keeps the array alive as long as it lives itself."""
     return ctypes.cast((ctype * len(values))(*values), ctypes.c_void_p)
+
+
+def workspace(nbytes, device):
+    """Device scratch for a `*_ws_bytes` / `*_bytes` size query, for callers that only pass its pointer on: a uint8 tensor of the queried
+    size, never fewer bytes than asked for and never empty (16 at the least, so that the pointer is not null)."""
+    import torch
+    return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)
 
 
 def ver(t):

@@ -144,7 +144,7 @@ class _TemporalAttentionFn(torch.autograd.Function):
         n_clips = F_ // T
         qkv_all = qkv(x).contiguous()
         res = torch.empty((F_, Vg, C), dtype=torch.float32, device=x.device)
-        scratch = torch.empty(_lib.lib().g4d_temporal_attention_scratch_floats(n_clips, Vg, C), dtype=torch.float32, device=x.device)
+        scratch = _lib.workspace(4 * _lib.lib().g4d_temporal_attention_scratch_floats(n_clips, Vg, C), x.device)
         att = torch.empty((n_clips, T, T), dtype=torch.float32, device=x.device)
         _lib.call("g4d_temporal_attention_f32", n_clips, T, Vg, C, qkv_all.data_ptr(), scratch.data_ptr(), att.data_ptr(), res.data_ptr(), C, 0,
                   _lib.stream_ptr())
@@ -161,7 +161,7 @@ class _TemporalAttentionFn(torch.autograd.Function):
         n_clips, rows = F_ // T, F_ * Vg
         dout, ldg = grad_ops.grad_window(dout, C)
         dqkv = torch.empty_like(qkv_all)
-        scratch = torch.empty(_lib.lib().g4d_temporal_attention_grad_scratch_floats(n_clips, Vg, C), dtype=torch.float32, device=x.device)
+        scratch = _lib.workspace(4 * _lib.lib().g4d_temporal_attention_grad_scratch_floats(n_clips, Vg, C), x.device)
         _lib.call("g4d_temporal_attention_grad_f32", n_clips, T, Vg, C, qkv_all.data_ptr(), att.data_ptr(), dout.data_ptr(), ldg, 0, scratch.data_ptr(),
                   dqkv.data_ptr(), _lib.stream_ptr())
         dx = dw = None
@@ -211,8 +211,7 @@ def temporal_attention(last_feat_local: torch.Tensor, frame_ids_local: torch.Ten
         qkv_all = qkv_all.contiguous()
         direct = out is not None and not sharded
         res = out if direct else torch.empty((F_, Vg, C), dtype=torch.float32, device=feats.device)
-        nscr = _lib.lib().g4d_temporal_attention_scratch_floats(n_clips, Vg, C)
-        scratch = torch.empty(nscr, dtype=torch.float32, device=feats.device)
+        scratch = _lib.workspace(4 * _lib.lib().g4d_temporal_attention_scratch_floats(n_clips, Vg, C), feats.device)
         att = torch.empty((n_clips, T, T), dtype=torch.float32, device=feats.device)
         _lib.call("g4d_temporal_attention_f32", n_clips, T, Vg, C, qkv_all.data_ptr(), scratch.data_ptr(), att.data_ptr(), res.data_ptr(),
                   res.shape[-1], col0 if direct else 0, _lib.stream_ptr())

@@ -35,6 +35,19 @@ def _ptr(t):
     return 0 if t is None else t.data_ptr()
 
 
+# host arrays in the form the C ABI takes them (_lib.host_array)
+def _floats(values):
+    return _lib.host_array(ctypes.c_float, [float(v) for v in values])
+
+
+def _ints(values):
+    return _lib.host_array(ctypes.c_int, [int(v) for v in values])
+
+
+def _ptrs(tensors):
+    return _lib.host_array(ctypes.c_void_p, [t.data_ptr() for t in tensors])
+
+
 def _chk(t, dtype=torch.float32):
     assert t.is_cuda and t.dtype == dtype and t.is_contiguous(), "fused path needs contiguous HIP tensors"
     return t
@@ -341,10 +354,8 @@ def wave_fits(layers, pool, S):
 def layer_arrays(layers, weight="Wf"):
     """The six per-layer host arrays of the whole-stack entry points, (W, scale, shift, Kpad, Cout, relu), of packed layers; `weight` names the
     layout the kernel family reads (Wf | Wf16 | Wc16)."""
-    ptrs = lambda tensors: _lib.host_array(ctypes.c_void_p, [t.data_ptr() for t in tensors])
-    ints = lambda values: _lib.host_array(ctypes.c_int, values)
-    return (ptrs([getattr(L, weight) for L in layers]), ptrs([L.scale for L in layers]), ptrs([L.shift for L in layers]),
-            ints([L.Kpad for L in layers]), ints([L.Cout for L in layers]), ints([L.relu for L in layers]))
+    return (_ptrs([getattr(L, weight) for L in layers]), _ptrs([L.scale for L in layers]), _ptrs([L.shift for L in layers]),
+            _ints([L.Kpad for L in layers]), _ints([L.Cout for L in layers]), _ints([L.relu for L in layers]))
 
 
 def mlp_stack(mode, rows, K0, layers, out, col0=0, pool=0, S=1, X=None, ldx=0, group=None, interp=None, csr=None, tap=None, cells_grid=None):
@@ -385,11 +396,11 @@ def mlp_stack(mode, rows, K0, layers, out, col0=0, pool=0, S=1, X=None, ldx=0, g
     if current_precision() == "bf16" and chain_fits(layers, pool, S, mode, bf16=True):   # register-chain bf16 kernel: any launch size, no LDS
         if mode == 2 and cells_grid is not None:
             a.unknown_grid = cells_grid.data_ptr()       # rows walked in the cell order of the unknown cloud's grid (same bits)
-        return run(_lib.MLP_CHAIN_BF16, _lib.host_array(ctypes.c_void_p, [L.Wc16.data_ptr() for L in layers]))
+        return run(_lib.MLP_CHAIN_BF16, _ptrs([L.Wc16 for L in layers]))
     if current_precision() == "bf16x3" and chain_fits(layers, pool, S, mode, bf16=True):
-        return run(_lib.MLP_CHAIN_BF16X3, _lib.host_array(ctypes.c_void_p, [t.data_ptr() for L in layers for t in L.Wc16x3()]))
+        return run(_lib.MLP_CHAIN_BF16X3, _ptrs([t for L in layers for t in L.Wc16x3()]))
     if _use_bf16(rows):
-        return run(_lib.MLP_STACK_BF16, _lib.host_array(ctypes.c_void_p, [L.Wf16.data_ptr() for L in layers]))
+        return run(_lib.MLP_STACK_BF16, _ptrs([L.Wf16 for L in layers]))
     if current_precision() in ("fp32", "bf16x3") and chain_fits(layers, pool, S, mode, bf16=False):
         return run(_lib.MLP_CHAIN_F32, Wp)
     if tap is None and wave_fits(layers, pool, S):
@@ -450,7 +461,7 @@ def build_ball_grid(xyz, rmax):
     (xyz, rmax) only -- reusable by every ball query on this cloud with radii <= rmax."""
     _chk(xyz)
     B, N, _ = xyz.shape
-    ws = torch.empty(max(_lib.lib().g4d_ball_grid_bytes(B, N), 16), dtype=torch.uint8, device=xyz.device)
+    ws = _lib.workspace(_lib.lib().g4d_ball_grid_bytes(B, N), xyz.device)
     _lib.call("g4d_ball_grid_build_f32", B, N, float(rmax), xyz.data_ptr(), ws.data_ptr(), _lib.stream_ptr())
     return ws, float(rmax)
 
@@ -460,7 +471,6 @@ def ball_query_msg(radii, nsamples, xyz, new_xyz, coherent=False, grid=None):
     coherent=True: the cloud's index order is spatially coherent (mesh vertices) -> block-bounds skipping (same results).
     grid: None = automatic (cell grid for clouds of >= Tuning.grid_min_n points), False = scan, True = build a grid, or a
     (workspace, rmax) pair from build_ball_grid.  Every route returns the same indices, bit for bit."""
-    import ctypes
     B, N, _ = xyz.shape
     P = new_xyz.shape[1]
     outs = [torch.empty((B, P, ns), dtype=torch.int32, device=xyz.device) for ns in nsamples]
@@ -471,24 +481,18 @@ def ball_query_msg(radii, nsamples, xyz, new_xyz, coherent=False, grid=None):
     done = 0
     while done < len(radii):  # the kernels take up to 4 scales per launch
         n = min(4, len(radii) - done)
-        R = (ctypes.c_float * n)(*[float(r) for r in radii[done:done + n]])
-        NS = (ctypes.c_int * n)(*[int(v) for v in nsamples[done:done + n]])
-        IP = (ctypes.c_void_p * n)(*[o.data_ptr() for o in outs[done:done + n]])
+        R, NS, IP = _floats(radii[done:done + n]), _ints(nsamples[done:done + n]), _ptrs(outs[done:done + n])
         if grid:
-            _lib.call("g4d_ball_grid_query_f32", B, N, P, n, ctypes.cast(R, ctypes.c_void_p), ctypes.cast(NS, ctypes.c_void_p),
-                      new_xyz.data_ptr(), xyz.data_ptr(), ctypes.cast(IP, ctypes.c_void_p), grid[0].data_ptr(), grid[1], _lib.stream_ptr())
+            _lib.call("g4d_ball_grid_query_f32", B, N, P, n, R, NS, new_xyz.data_ptr(), xyz.data_ptr(), IP, grid[0].data_ptr(), grid[1], _lib.stream_ptr())
         elif coherent and N >= 256:
             boxes = torch.empty((B, (N + 15) // 16, 6), dtype=torch.float32, device=xyz.device)   # 16-point sub-block bounds
             if _T().coherent_lanes:   # one lane per query; the queries are cell-sorted first so that a wave's 64 are compact
-                qs = torch.empty(max(_lib.lib().g4d_ball_query_lanes_qsort_bytes(B, P), 16), dtype=torch.uint8, device=xyz.device) if _T().lanes_sort else None
-                _lib.call("g4d_ball_query_lanes_f32", B, N, P, n, ctypes.cast(R, ctypes.c_void_p), ctypes.cast(NS, ctypes.c_void_p),
-                          new_xyz.data_ptr(), xyz.data_ptr(), ctypes.cast(IP, ctypes.c_void_p), boxes.data_ptr(), _ptr(qs), _lib.stream_ptr())
+                qs = _lib.workspace(_lib.lib().g4d_ball_query_lanes_qsort_bytes(B, P), xyz.device) if _T().lanes_sort else None
+                _lib.call("g4d_ball_query_lanes_f32", B, N, P, n, R, NS, new_xyz.data_ptr(), xyz.data_ptr(), IP, boxes.data_ptr(), _ptr(qs), _lib.stream_ptr())
             else:
-                _lib.call("g4d_ball_query_boxes_f32", B, N, P, n, ctypes.cast(R, ctypes.c_void_p), ctypes.cast(NS, ctypes.c_void_p),
-                          new_xyz.data_ptr(), xyz.data_ptr(), ctypes.cast(IP, ctypes.c_void_p), boxes.data_ptr(), _lib.stream_ptr())
+                _lib.call("g4d_ball_query_boxes_f32", B, N, P, n, R, NS, new_xyz.data_ptr(), xyz.data_ptr(), IP, boxes.data_ptr(), _lib.stream_ptr())
         else:
-            _lib.call("g4d_ball_query_msg_f32", B, N, P, n, ctypes.cast(R, ctypes.c_void_p), ctypes.cast(NS, ctypes.c_void_p),
-                      new_xyz.data_ptr(), xyz.data_ptr(), ctypes.cast(IP, ctypes.c_void_p), _lib.stream_ptr())
+            _lib.call("g4d_ball_query_msg_f32", B, N, P, n, R, NS, new_xyz.data_ptr(), xyz.data_ptr(), IP, _lib.stream_ptr())
         done += n
     return outs
 
@@ -512,7 +516,7 @@ def fps_gather_grid(xyz, npoint, rmax):
         return fps_gather(xyz, npoint), build_ball_grid(xyz, rmax)
     sidx = torch.empty((B, npoint), dtype=torch.int32, device=xyz.device)
     new_xyz = torch.empty((B, npoint, 3), dtype=torch.float32, device=xyz.device)
-    ws = torch.empty(max(_lib.lib().g4d_ball_grid_bytes(B, N), 16), dtype=torch.uint8, device=xyz.device)
+    ws = _lib.workspace(_lib.lib().g4d_ball_grid_bytes(B, N), xyz.device)
     _lib.call("g4d_fps_gather_grid_f32", B, N, npoint, xyz.data_ptr(), sidx.data_ptr(), new_xyz.data_ptr(), float(rmax), ws.data_ptr(), _lib.stream_ptr())
     return new_xyz, (ws, float(rmax))
 
@@ -536,44 +540,44 @@ def fps_gather_pair(xyz, m1, m2):
 # (BQ_MULTI -> tuning.Tuning.bq_multi) the ball queries of two small SA levels in one launch
 
 
+def _query_pair(q0, q1):
+    """The outputs and the shared argument run of two multi-scale ball queries q = (radii, nsamples, xyz, new_xyz) with the same batch size
+    and number of scales, as g4d_ball_query_msg2_f32 and g4d_search_multi_f32 take them: (o0, o1, [B, nscales, N0, P0, ..., idx1])."""
+    assert len(q0[0]) == len(q1[0]) and q0[2].shape[0] == q1[2].shape[0]
+    outs, args = [], [q0[2].shape[0], len(q0[0])]
+    for radii, nsamples, xyz, new_xyz in (q0, q1):
+        o = [torch.empty((xyz.shape[0], new_xyz.shape[1], k), dtype=torch.int32, device=q0[2].device) for k in nsamples]
+        outs.append(o)
+        args += [xyz.shape[1], new_xyz.shape[1], _floats(radii), _ints(nsamples), _chk(new_xyz).data_ptr(), _chk(xyz).data_ptr(), _ptrs(o)]
+    return outs[0], outs[1], args
+
+
 def ball_query_msg2(q0, q1):
     """Two multi-scale ball queries in one launch: q = (radii, nsamples, xyz, new_xyz), same batch size and number of scales; returns the
     two lists of (B,P,nsample) int32 tensors ball_query_msg would (g4d_ball_query_msg2_f32; scan route only)."""
-    (r0, s0, x0, c0), (r1, s1, x1, c1) = q0, q1
-    assert len(r0) == len(r1) and x0.shape[0] == x1.shape[0]
-    B, ns = x0.shape[0], len(r0)
-    o0 = [torch.empty((B, c0.shape[1], k), dtype=torch.int32, device=x0.device) for k in s0]
-    o1 = [torch.empty((B, c1.shape[1], k), dtype=torch.int32, device=x0.device) for k in s1]
-    FA, IA, PA = ctypes.c_float * ns, ctypes.c_int * ns, ctypes.c_void_p * ns
-    vp = lambda a: ctypes.cast(a, ctypes.c_void_p)
-    _lib.call("g4d_ball_query_msg2_f32", B, ns, x0.shape[1], c0.shape[1], vp(FA(*[float(r) for r in r0])), vp(IA(*[int(k) for k in s0])), _chk(c0).data_ptr(),
-              _chk(x0).data_ptr(), vp(PA(*[o.data_ptr() for o in o0])), x1.shape[1], c1.shape[1], vp(FA(*[float(r) for r in r1])), vp(IA(*[int(k) for k in s1])),
-              _chk(c1).data_ptr(), _chk(x1).data_ptr(), vp(PA(*[o.data_ptr() for o in o1])), _lib.stream_ptr())
+    o0, o1, args = _query_pair(q0, q1)
+    _lib.call("g4d_ball_query_msg2_f32", *args, _lib.stream_ptr())
     return o0, o1
 
 
 # (SEARCH_MULTI -> tuning.Tuning.search_multi) the inner levels' ball queries AND three-NN searches in one launch
 
 
-def search_multi(q0, q1, pairs):
-    """ball_query_msg2(q0, q1) and three_nn_multi(pairs) in ONE launch (g4d_search_multi_f32): returns (o0, o1, [(dist2, idx), ...])."""
-    (r0, s0, x0, c0), (r1, s1, x1, c1) = q0, q1
-    assert len(r0) == len(r1) and x0.shape[0] == x1.shape[0] and 1 <= len(pairs) <= 4
-    B, ns = x0.shape[0], len(r0)
-    dev = x0.device
-    o0 = [torch.empty((B, c0.shape[1], k), dtype=torch.int32, device=dev) for k in s0]
-    o1 = [torch.empty((B, c1.shape[1], k), dtype=torch.int32, device=dev) for k in s1]
+def _nn_pairs(pairs, B, dev):
+    """The outputs and the argument run of the three-NN searches (unknown, known) of `pairs`, as g4d_three_nn_multi_f32 and
+    g4d_search_multi_f32 take them: ([(dist2, idx), ...], [n, m, unknown, known, dist2, idx] as host arrays)."""
     outs = [(torch.empty((B, _chk(u).shape[1], 3), dtype=torch.float32, device=dev), torch.empty((B, u.shape[1], 3), dtype=torch.int32, device=dev))
             for u, k in pairs]
-    FA, IA, PA = ctypes.c_float * ns, ctypes.c_int * ns, ctypes.c_void_p * ns
-    c = len(pairs)
-    IC, PC = ctypes.c_int * c, ctypes.c_void_p * c
-    vp = lambda a: ctypes.cast(a, ctypes.c_void_p)
-    _lib.call("g4d_search_multi_f32", B, ns, x0.shape[1], c0.shape[1], vp(FA(*[float(r) for r in r0])), vp(IA(*[int(k) for k in s0])), _chk(c0).data_ptr(),
-              _chk(x0).data_ptr(), vp(PA(*[o.data_ptr() for o in o0])), x1.shape[1], c1.shape[1], vp(FA(*[float(r) for r in r1])), vp(IA(*[int(k) for k in s1])),
-              _chk(c1).data_ptr(), _chk(x1).data_ptr(), vp(PA(*[o.data_ptr() for o in o1])), c, vp(IC(*[u.shape[1] for u, k in pairs])),
-              vp(IC(*[_chk(k).shape[1] for u, k in pairs])), vp(PC(*[u.data_ptr() for u, k in pairs])), vp(PC(*[k.data_ptr() for u, k in pairs])),
-              vp(PC(*[o[0].data_ptr() for o in outs])), vp(PC(*[o[1].data_ptr() for o in outs])), _lib.stream_ptr())
+    return outs, [_ints([u.shape[1] for u, k in pairs]), _ints([_chk(k).shape[1] for u, k in pairs]), _ptrs([u for u, k in pairs]),
+                  _ptrs([k for u, k in pairs]), _ptrs([o[0] for o in outs]), _ptrs([o[1] for o in outs])]
+
+
+def search_multi(q0, q1, pairs):
+    """ball_query_msg2(q0, q1) and three_nn_multi(pairs) in ONE launch (g4d_search_multi_f32): returns (o0, o1, [(dist2, idx), ...])."""
+    assert 1 <= len(pairs) <= 4
+    o0, o1, args = _query_pair(q0, q1)
+    outs, nn_args = _nn_pairs(pairs, q0[2].shape[0], q0[2].device)
+    _lib.call("g4d_search_multi_f32", *args, len(pairs), *nn_args, _lib.stream_ptr())
     return o0, o1, outs
 
 
@@ -704,7 +708,7 @@ def sa_scale_mlp(xyz, new_xyz, feats_pm, idx, layers, use_xyz, pool, out, col0, 
         L0, rest = layers[0], layers[1:]
         # scratch for the widest stack's work list (round 6: blocks of ball-query padding are not computed; csrc/sa_table.hip) -- 0 bytes for every other shape
         nws = int(_lib.lib().g4d_sa_table_ws_bytes(B * P * S, L0.Cout, S, pool)) if len(rest) == 2 else 0
-        ws = torch.empty((nws + 3) // 4, dtype=torch.int32, device=xyz.device) if nws > 0 else None
+        ws = _lib.workspace(nws, xyz.device) if nws > 0 else None
         _lib.call("g4d_mlp_chain_group_table_ws_f32", B * P * S, N, P, S, xyz.data_ptr(), new_xyz.data_ptr(), idx.data_ptr(),
                   tab.data_ptr() + 4 * c0, tab.shape[-1] if tab_ld is None else tab_ld, L0.Cout, wxT.data_ptr(), L0.scale.data_ptr(), L0.shift.data_ptr(), len(rest),
                   *layer_arrays(rest), pool, out.data_ptr(), out.shape[-1], col0, _ptr(ws), nws, stream)
@@ -840,7 +844,7 @@ def three_nn_pruned(unknown, unknown_grid, known, dist2, nn_idx, sorted_out):
     B, n = dist2.shape[0], dist2.shape[1]
     m = known.shape[1]
     nws = int(_lib.lib().g4d_three_nn_pruned_ws_bytes(B))
-    ws = torch.empty((max(nws, 16) + 3) // 4, dtype=torch.float32, device=known.device)   # sorted records + block boxes, 18 KB per cloud
+    ws = _lib.workspace(nws, known.device)   # sorted records + block boxes, 18 KB per cloud
     _lib.call("g4d_three_nn_pruned_f32", B, n, m, _ptr(unknown), 0 if unknown_grid is None else unknown_grid[0].data_ptr(), known.data_ptr(),
               dist2.data_ptr(), nn_idx.data_ptr(), int(bool(sorted_out)), ws.data_ptr(), nws, _lib.stream_ptr())
 
@@ -867,7 +871,7 @@ def three_nn(unknown, known, dist2=None, nn_idx=None, grid=None, unknown_grid=No
     if grid is None:
         grid = m >= _T().three_nn_grid_min_m
     if grid and m > 0 and B * n > 0:
-        ws = torch.empty(max(_lib.lib().g4d_ball_grid_bytes(B, m), 16), dtype=torch.uint8, device=dev)
+        ws = _lib.workspace(_lib.lib().g4d_ball_grid_bytes(B, m), dev)
         _lib.call("g4d_three_nn_grid_f32", B, n, m, unknown.data_ptr(), known.data_ptr(), dist2.data_ptr(), nn_idx.data_ptr(), ws.data_ptr(),
                   _lib.stream_ptr())
     else:
@@ -882,16 +886,8 @@ def three_nn_multi(pairs):
     """[(unknown (B,n_i,3), known (B,m_i,3)), ...] (up to 4, same B) -> [(dist2, idx), ...] in one launch (g4d_three_nn_multi_f32);
     each result equals three_nn(unknown, known)."""
     assert 1 <= len(pairs) <= 4
-    B = pairs[0][0].shape[0]
-    dev = pairs[0][0].device
-    outs = [(torch.empty((B, _chk(u).shape[1], 3), dtype=torch.float32, device=dev), torch.empty((B, u.shape[1], 3), dtype=torch.int32, device=dev))
-            for u, k in pairs]
-    c = len(pairs)
-    IA, PA = ctypes.c_int * c, ctypes.c_void_p * c
-    _lib.call("g4d_three_nn_multi_f32", B, c, ctypes.cast(IA(*[u.shape[1] for u, k in pairs]), ctypes.c_void_p),
-              ctypes.cast(IA(*[_chk(k).shape[1] for u, k in pairs]), ctypes.c_void_p), ctypes.cast(PA(*[u.data_ptr() for u, k in pairs]), ctypes.c_void_p),
-              ctypes.cast(PA(*[k.data_ptr() for u, k in pairs]), ctypes.c_void_p), ctypes.cast(PA(*[o[0].data_ptr() for o in outs]), ctypes.c_void_p),
-              ctypes.cast(PA(*[o[1].data_ptr() for o in outs]), ctypes.c_void_p), _lib.stream_ptr())
+    outs, args = _nn_pairs(pairs, pairs[0][0].shape[0], pairs[0][0].device)
+    _lib.call("g4d_three_nn_multi_f32", pairs[0][0].shape[0], len(pairs), *args, _lib.stream_ptr())
     return outs
 
 
@@ -924,7 +920,7 @@ def fp_table_layer(fp, C1, C2, head):
     if not (_T().fp_table and C1 == 0 and C2 % 16 == 0 and layers[0].relu and layers[0].Cout % 16 == 0 and current_precision() == "fp32" and _T().use_chain):
         return None
     rest = layers[1:] + (pack_conv_stack(head) if head is not None else [])
-    if not rest or not _lib.lib().g4d_mlp_chain_supported(len(rest), (ctypes.c_int * len(rest))(*[L.Cout for L in rest])):
+    if not rest or not _lib.lib().g4d_mlp_chain_supported(len(rest), _ints([L.Cout for L in rest])):
         return None
     return layers[0].raw()
 
@@ -967,7 +963,7 @@ def fp_forward(fp, unknown, known, unknow_feats_pm, known_feats_pm, head=None, u
              and B > 0 and C2 % 16 == 0 and layers[0].relu and layers[0].Cout % 16 == 0 and current_precision() == "fp32" and _T().use_chain)
     if cells:
         rest_ = layers[1:] + (pack_conv_stack(head) if head is not None else [])
-        cells = bool(rest_) and bool(_lib.lib().g4d_mlp_chain_supported(len(rest_), (ctypes.c_int * len(rest_))(*[L.Cout for L in rest_])))
+        cells = bool(rest_) and bool(_lib.lib().g4d_mlp_chain_supported(len(rest_), _ints([L.Cout for L in rest_])))
     if cells:
         dist2 = torch.empty((B, n, 3), dtype=torch.float32, device=unknown.device)
         nn_idx = torch.empty((B, n, 3), dtype=torch.int32, device=unknown.device)
@@ -988,7 +984,7 @@ def fp_forward(fp, unknown, known, unknow_feats_pm, known_feats_pm, head=None, u
         # No skip features: conv(sum_i w_i f_i) = sum_i w_i conv(f_i), so the first layer's contraction runs over the m KNOWN rows
         # (table) instead of the n interpolated ones, and the layer itself becomes relu(interp(table) * scale + shift) in the loader.
         rest = layers[1:] + (pack_conv_stack(head) if head is not None else [])
-        if rest and _lib.lib().g4d_mlp_chain_supported(len(rest), (ctypes.c_int * len(rest))(*[L.Cout for L in rest])):
+        if rest and _lib.lib().g4d_mlp_chain_supported(len(rest), _ints([L.Cout for L in rest])):
             L0 = layers[0]
             if table is None:   # (else: computed by the launch that produced known_feats_pm, fp_forward(..., also_table=fp_table_layer(...)))
                 table = linear(known_feats_pm.view(B * m, C2), L0.raw())

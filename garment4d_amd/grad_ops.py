@@ -22,7 +22,7 @@ def col_sum(rows, c, g, mask=None):
     """Column sums (c,) of the (rows, c) matrix g, of the entries where mask > 0 when a mask (the output of a fused ReLU) is given:
     g4d_col_sum_rows_f32."""
     out = torch.empty(c, dtype=torch.float32, device=g.device)
-    ws = torch.empty(max(int(_lib.lib().g4d_col_sum_rows_ws_bytes(rows, c)) // 4, 1), dtype=torch.float32, device=g.device)
+    ws = _lib.workspace(_lib.lib().g4d_col_sum_rows_ws_bytes(rows, c), g.device)
     _lib.call("g4d_col_sum_rows_f32", rows, c, g.data_ptr(), 0 if mask is None else mask.data_ptr(), ws.data_ptr(), out.data_ptr(),
               _lib.stream_ptr())
     return out
@@ -32,7 +32,7 @@ def gemm_tn(rows, fin, ldx, cout, x, ds):
     """X^T dS (fin, cout) over `rows` rows, X being the first fin columns of rows ldx >= fin apart: g4d_gemm_tn_f32, slice partials added
     in a fixed order."""
     dw = torch.empty((fin, cout), dtype=torch.float32, device=x.device)
-    ws = torch.empty(max(int(_lib.lib().g4d_gemm_tn_ws_bytes(rows, fin, cout)) // 4, 1), dtype=torch.float32, device=x.device)
+    ws = _lib.workspace(_lib.lib().g4d_gemm_tn_ws_bytes(rows, fin, cout), x.device)
     _lib.call("g4d_gemm_tn_f32", rows, fin, ldx, cout, x.data_ptr(), ds.data_ptr(), ws.data_ptr(), dw.data_ptr(), _lib.stream_ptr())
     return dw
 
@@ -57,16 +57,12 @@ def linear_t(ds2d, weight):
     return fused.linear(ds2d, L)
 
 
-def _ws(nbytes, device):
-    return torch.empty(max(int(nbytes) // 4, 1), dtype=torch.float32, device=device)
-
-
 def bn_stats(rows, c, y, ldy):
     """(mean, biased variance), each (c,), over the rows of the first c columns of y (rows ldy >= c apart): g4d_bn_stats_f32, two passes, slice
     partials added in a fixed order."""
     mean = torch.empty(c, dtype=torch.float32, device=y.device)
     var = torch.empty(c, dtype=torch.float32, device=y.device)
-    ws = _ws(_lib.lib().g4d_bn_stats_ws_bytes(rows, c), y.device)
+    ws = _lib.workspace(_lib.lib().g4d_bn_stats_ws_bytes(rows, c), y.device)
     _lib.call("g4d_bn_stats_f32", rows, c, y.data_ptr(), ldy, ws.data_ptr(), mean.data_ptr(), var.data_ptr(), _lib.stream_ptr())
     return mean, var
 
@@ -84,7 +80,7 @@ def bn_act_grad_reduce(rows, c, dout, ldg, y, ldy, mean, var, eps, gamma, beta, 
     """(dgamma, dbeta) = (sum G * xhat, sum G) with G = dout where the activation passed: g4d_bn_act_grad_reduce_f32 (mask and xhat recomputed from y)."""
     dgamma = torch.empty(c, dtype=torch.float32, device=y.device)
     dbeta = torch.empty(c, dtype=torch.float32, device=y.device)
-    ws = _ws(_lib.lib().g4d_bn_act_grad_reduce_ws_bytes(rows, c), y.device)
+    ws = _lib.workspace(_lib.lib().g4d_bn_act_grad_reduce_ws_bytes(rows, c), y.device)
     _lib.call("g4d_bn_act_grad_reduce_f32", rows, c, dout.data_ptr(), ldg, y.data_ptr(), ldy, mean.data_ptr(), var.data_ptr(), float(eps),
               fused._ptr(gamma), fused._ptr(beta), int(relu), ws.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), _lib.stream_ptr())
     return dgamma, dbeta

@@ -177,7 +177,7 @@ def lbs(betas, pose, v_template, shapedirs, posedirs, J_regressor, parents, lbs_
     if _T().lbs_fused and _T().lbs_mfma and V > 0 and _lib.lib().g4d_lbs_mfma_supported(J, NB):
         blend_dirs, Jt, Js = _model_constants(v_template, shapedirs, posedirs, J_regressor)
         nws = int(_lib.lib().g4d_lbs_mfma_ws_bytes(B, J))
-        ws = torch.empty((max(nws, 16) + 3) // 4, dtype=torch.float32, device=dev)   # the GEMMs' B operands (2.4 KB per frame); the allocator's blocks are 512-byte aligned
+        ws = _lib.workspace(nws, dev)   # the GEMMs' B operands (2.4 KB per frame); the allocator's blocks are 512-byte aligned
         _lib.call("g4d_lbs_mfma_f32", B, V, J, NB, int(bool(pose2rot)), betas.data_ptr(), NB if betas.shape[0] == B else 0, pose.data_ptr(),
                   v_template.data_ptr(), blend_dirs.data_ptr(), Jt.data_ptr(), Js.data_ptr(), _parents_i32(parents, dev).data_ptr(),
                   lbs_weights.data_ptr(), A.data_ptr(), posed.data_ptr(), verts.data_ptr(), ws.data_ptr(), nws, stream)

@@ -94,9 +94,7 @@ def _evaluate_rounds(rounds, want, target, body_v, body_vn, csr, nbatch, T, weig
     dev = body_v.device
     vals = torch.empty((R, 5), dtype=torch.float32, device=dev)
     msre = torch.empty((F_,), dtype=torch.float32, device=dev)
-    ws_grad = max(int(_lib.lib().g4d_refine_loss_ws_bytes(F_, Vg, 1)) // 4, 1)
-    ws_vals = max(int(_lib.lib().g4d_refine_loss_ws_bytes(F_, Vg, 0)) // 4, 1)
-    ws = torch.empty(ws_grad if any(want) else ws_vals, dtype=torch.float32, device=dev)   # one workspace: the rounds run in stream order
+    ws = _lib.workspace(_lib.lib().g4d_refine_loss_ws_bytes(F_, Vg, int(any(want))), dev)   # one workspace: the rounds run in stream order
     grads = []
     st = _lib.stream_ptr()
     for r, p in enumerate(rounds):
@@ -260,7 +258,7 @@ def _evaluate_stage1(logits, coeff, pred, want, consts):
     rows = x.numel() // C if C else 0
     assert labels.numel() == rows, "one label per row of logits"
     g_logits = torch.empty_like(x) if want[0] else None
-    ws = torch.empty(max(int(L.g4d_stage1_loss_ws_bytes(rows, 0, 0, 0, 0)) // 4, 1), dtype=torch.float32, device=dev)
+    ws = _lib.workspace(L.g4d_stage1_loss_ws_bytes(rows, 0, 0, 0, 0), dev)
     _lib.call("g4d_stage1_ce_f32", rows, C, x.data_ptr(), labels.data_ptr(), weights[0], ws.data_ptr(), vals.data_ptr(),
               0 if g_logits is None else g_logits.data_ptr(), st)
     if only_seg:
@@ -274,7 +272,7 @@ def _evaluate_stage1(logits, coeff, pred, want, consts):
     idx = fused.three_nn(q, body_v)[1] if B * Vg else torch.zeros((B, Vg, 3), dtype=torch.int32, device=dev)
     g_coeff = torch.empty_like(a) if want[1] else None
     g_pred = torch.empty_like(p) if want[2] else None
-    ws = torch.empty(max(int(L.g4d_stage1_loss_ws_bytes(0, B, Vg, nf, int(want[2]))) // 4, 1), dtype=torch.float32, device=dev)
+    ws = _lib.workspace(L.g4d_stage1_loss_ws_bytes(0, B, Vg, nf, int(want[2])), dev)
     out = torch.empty(5, dtype=torch.float32, device=dev)
     _lib.call("g4d_stage1_garment_f32", B, pad_batch, Vg, V, nf, P, p.data_ptr(), target.data_ptr(), root.data_ptr(), body_v.data_ptr(), body_vn.data_ptr(),
               idx.data_ptr(), 3, faces.data_ptr(), rowptr.data_ptr(), entries.data_ptr(), a.data_ptr(), coeff_gt.data_ptr(), weights[1], weights[2],

@@ -18,7 +18,7 @@ import contextlib
 
 from . import _lib
 
-MODES = {"off": 0, "nvcc": 1, "chain": 2}
+MODES = {m: _lib.CONSTANTS["G4D_CONTRACT_" + m.upper()] for m in ("off", "nvcc", "chain")}   # include/g4d.h
 _NAMES = {v: k for k, v in MODES.items()}
 
 

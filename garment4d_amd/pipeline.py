@@ -154,11 +154,9 @@ class StepPipeline:
             pairs = [(s.cloud[sl], cloud)] if self.smpl is None else [(s.cloud[sl], cloud), (s.betas[sl], betas), (s.pose[sl], pose)]
             ok = all(src.is_cuda and src.dtype == torch.float32 and src.is_contiguous() and src.numel() == dst.numel() for dst, src in pairs)
             if ok:
-                n = len(pairs)
-                PA, LA = ctypes.c_void_p * n, ctypes.c_longlong * n
-                _lib.call("g4d_copy_segments_f32", n, ctypes.cast(PA(*[d.data_ptr() for d, _ in pairs]), ctypes.c_void_p),
-                          ctypes.cast(PA(*[x.data_ptr() for _, x in pairs]), ctypes.c_void_p),
-                          ctypes.cast(LA(*[d.numel() for d, _ in pairs]), ctypes.c_void_p), _lib.stream_ptr())
+                _lib.call("g4d_copy_segments_f32", len(pairs), _lib.host_array(ctypes.c_void_p, [d.data_ptr() for d, _ in pairs]),
+                          _lib.host_array(ctypes.c_void_p, [x.data_ptr() for _, x in pairs]),
+                          _lib.host_array(ctypes.c_longlong, [d.numel() for d, _ in pairs]), _lib.stream_ptr())
             else:   # host tensors, other dtypes / strides: the runtime's copies
                 for dst, src in pairs:
                     dst.copy_(src.reshape(dst.shape), non_blocking=True)

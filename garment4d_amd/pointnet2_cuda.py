@@ -72,9 +72,8 @@ def ball_query_wrapper(b, n, m, radius, nsample, new_xyz, xyz, idx):
         # (legal in the reference: every row stays zero) and radius inf take the scan below like small clouds do.
         import ctypes
         ws = _workspace(_lib.lib().g4d_ball_grid_bytes(b, n), xyz.device)
-        R, NS, IP = (ctypes.c_float * 1)(float(radius)), (ctypes.c_int * 1)(int(nsample)), (ctypes.c_void_p * 1)(pi)
-        _lib.call("g4d_ball_query_grid_f32", b, n, m, 1, ctypes.cast(R, ctypes.c_void_p), ctypes.cast(NS, ctypes.c_void_p), pq, px,
-                  ctypes.cast(IP, ctypes.c_void_p), ws.data_ptr(), _lib.stream_ptr())
+        _lib.call("g4d_ball_query_grid_f32", b, n, m, 1, _lib.host_array(ctypes.c_float, [float(radius)]), _lib.host_array(ctypes.c_int, [int(nsample)]),
+                  pq, px, _lib.host_array(ctypes.c_void_p, [pi]), ws.data_ptr(), _lib.stream_ptr())
         return 1
     _lib.call("g4d_ball_query_f32", b, n, m, float(radius), nsample, pq, px, pi, _lib.stream_ptr())
     return 1

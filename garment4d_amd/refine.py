@@ -190,7 +190,7 @@ class _PosEncodeFn(torch.autograd.Function):
         db2 = torch.empty(32, **f32) if need[7] else None
         ws = None
         if dW1 is not None or db1 is not None or dW2 is not None or db2 is not None:
-            ws = torch.empty(max(int(_lib.lib().g4d_pos_encode_grad_ws_bytes(F_, Vg, S)) // 4, 1), **f32)
+            ws = _lib.workspace(_lib.lib().g4d_pos_encode_grad_ws_bytes(F_, Vg, S), dev)
         P = lambda t: 0 if t is None else t.data_ptr()
         b1c = None if table is not None else b1.detach().float().contiguous()   # with a table the bias sits in the table (NULL, as in the forward)
         _lib.call("g4d_pos_encode_grad_f32", F_, N, Vg, S, n_extra, xyz.data_ptr(), new_xyz.data_ptr(), P(extra) if n_extra else 0, P(table),

@@ -28,16 +28,50 @@ def test_library_exports_every_declared_symbol():
     assert L.g4d_version() >= 100
 
 
-def test_ctypes_signatures_cover_header():
+_LETTERS = {ctypes.c_int: "i", ctypes.c_float: "f", ctypes.c_longlong: "q", ctypes.c_size_t: "z", ctypes.c_uint: "u", ctypes.c_void_p: "p",
+            ctypes.c_char_p: "s"}
+
+
+def abi_snapshot():
+    """tests/abi_snapshot.txt, the reviewed record of the C ABI: ({entry point: "<return>:<one letter per parameter>"}, [(field, letter)] of
+    g4d_mlp_args).  Letters: i int, f float, q long long, z size_t, u unsigned, p pointer (g4d_stream_t included), s char pointer.  The record
+    was written from the hand-typed ctypes tables this binding had before it read the header, the ones every GPU test had run through."""
+    lines = [ln.split() for ln in open(os.path.join(ROOT, "tests", "abi_snapshot.txt")).read().splitlines()]
+    assert lines[-1][0] == "g4d_mlp_args" and all(len(ln) == 2 for ln in lines[:-1])
+    return dict(lines[:-1]), [tuple(f.split(":")) for f in lines[-1][1:]]
+
+
+def test_parsed_header_equals_the_abi_snapshot():
+    """include/g4d.h as _lib reads it == tests/abi_snapshot.txt, both ways and in the header's order: a changed prototype fails (the header's
+    own rule: entry points are added, none changed), a new one fails until its line is appended to the record."""
     from garment4d_amd import _lib
-    declared = set(declared_symbols()) - {"g4d_version", "g4d_last_error", "g4d_get_distance_contraction", "g4d_set_distance_contraction",
-                                          "g4d_set_distance_contraction_thread"}
-    assert declared == set(_lib.SIGNATURES), (declared ^ set(_lib.SIGNATURES))
+    protos, fields, _ = _lib.parse_header(open(os.path.join(ROOT, "include", "g4d.h")).read())
+    parsed = {n: _LETTERS[r] + ":" + "".join(_LETTERS[t] for t in a) for n, (r, a) in protos.items()}
+    recorded, rec_fields = abi_snapshot()
+    assert set(parsed) == set(declared_symbols()) and len(parsed) >= 131
+    assert {n: (parsed.get(n), recorded.get(n)) for n in set(parsed) | set(recorded) if parsed.get(n) != recorded.get(n)} == {}
+    assert list(parsed) == list(recorded)
+    assert [(n, _LETTERS[t]) for n, t in fields] == rec_fields
+    # the names other code reads are views of the same parse
+    assert _lib.SIGNATURES == {n: a for n, (r, a) in protos.items()}
+    assert _lib.RESTYPES == {n: r for n, (r, a) in protos.items() if r is not ctypes.c_int} and len(_lib.RESTYPES) == 20
+
+
+def test_loaded_library_carries_the_derived_types():
+    from garment4d_amd import _lib
+    L = _lib.lib()
+    recorded, _ = abi_snapshot()
+    for name, code in recorded.items():
+        fn = getattr(L, name)
+        assert _LETTERS[fn.restype] + ":" + "".join(_LETTERS[t] for t in fn.argtypes) == code, name
+        assert list(fn.argtypes) == _lib.SIGNATURES[name] and fn.restype is _lib.RESTYPES.get(name, ctypes.c_int), name
+    assert L.g4d_version() == 263 and isinstance(L.g4d_last_error(), bytes)
 
 
 def test_mlp_argument_block_mirrors_the_header():
-    """g4d_mlp_args (include/g4d.h) <-> _lib.MlpArgs: same size as the library compiled it, same field names in the same order, and the
-    library refuses a block of another version / a larger size instead of misreading it (no launch is made: the checks come first)."""
+    """g4d_mlp_args (include/g4d.h) <-> _lib.MlpArgs: same size as the library compiled it, same field names in the same order with the types
+    of the record, and the library refuses a block of another version / a larger size instead of misreading it (no launch is made: the
+    checks come first)."""
     from garment4d_amd import _lib
     L = _lib.lib()
     assert ctypes.sizeof(_lib.MlpArgs) == L.g4d_mlp_args_size()
@@ -52,6 +86,9 @@ def test_mlp_argument_block_mirrors_the_header():
         for piece in decl.split(","):
             names.append(re.findall(r"[A-Za-z_][A-Za-z0-9_]*", piece)[-1])
     assert names == [f for f, _ in _lib.MlpArgs._fields_], (names, [f for f, _ in _lib.MlpArgs._fields_])
+    assert [(f, _LETTERS[t]) for f, t in _lib.MlpArgs._fields_] == abi_snapshot()[1]
+    assert _lib.MLP_ARGS_VERSION == 1
+    assert (_lib.MLP_STACK_F32, _lib.MLP_STACK_BF16, _lib.MLP_WAVE_F32, _lib.MLP_CHAIN_F32, _lib.MLP_CHAIN_BF16, _lib.MLP_CHAIN_BF16X3) == tuple(range(6))
     a = _lib.MlpArgs()
     assert a.size == ctypes.sizeof(_lib.MlpArgs) and a.version == _lib.MLP_ARGS_VERSION and a.tap_layer == -1
     a.version = 99
@@ -92,6 +129,16 @@ def test_missing_library_fails_loudly(monkeypatch):
     monkeypatch.setattr(_lib, "_lib", None)
     monkeypatch.setattr(_lib, "LIB_PATH", "/nonexistent/libg4d_hip.so")
     with pytest.raises(_lib.G4DError):
+        _lib.lib()
+
+
+def test_missing_header_fails_loudly(monkeypatch):
+    """The binding is read from include/g4d.h when the library is loaded: no header, no binding -- and no table to fall back on."""
+    from garment4d_amd import _lib
+    monkeypatch.setattr(_lib, "_lib", None)
+    monkeypatch.setattr(_lib, "_header", None)
+    monkeypatch.setattr(_lib, "HEADER_PATH", "/nonexistent/include/g4d.h")
+    with pytest.raises(_lib.G4DError, match="/nonexistent/include/g4d.h"):
         _lib.lib()
 
 
