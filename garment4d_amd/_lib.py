@@ -7,6 +7,9 @@ this raises -- the product path never silently routes to PyTorch eager or to the
 Nothing of the ABI is typed here by hand: every prototype's argtypes and restype, the fields of `g4d_mlp_args` and the `G4D_*` constants
 are read from include/g4d.h when the library is loaded (`parse_header`), and tests/abi_snapshot.txt is the reviewed record of what that
 gives -- a changed or new entry point shows up there as a changed or new line.
+
+Further libraries of the package are (header, library) pairs of the same shape, loaded by load_pair(): the rasterizer, include/g4d_render.h +
+lib/libg4d_render.so (render_lib(); record: tests/render_abi_snapshot.txt).  call() serves them too.
 """
 import ctypes
 import os
@@ -17,8 +20,14 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("G4D_LIB_PATH") or os.path.join(_HERE, "lib", "libg4d_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "g4d.h")
 
+# the second (header, library) pair: the rasterizer (include/g4d_render.h, libg4d_render.so; render_lib() loads it).  It links against
+# libg4d_hip.so and reports through the same g4d_last_error().  The names PROTOTYPES, SIGNATURES, RESTYPES, _lib, _header stay g4d.h's alone.
+RENDER_LIB_PATH = os.path.join(_HERE, "lib", "libg4d_render.so")
+RENDER_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "g4d_render.h")
+
 _lib = None
 _header = None   # HEADER_PATH once the names below are bound from it
+_more = {}       # library path -> (its CDLL, {entry point: (restype, argtypes)}, its G4D_* constants) of every further pair load_pair() loaded
 
 
 class G4DError(RuntimeError):
@@ -136,6 +145,43 @@ def lib():
     return _lib
 
 
+def load_pair(header_path, lib_path):
+    """Load a further library once, typed as its own header declares it (the same parse as include/g4d.h's): call() then finds its entry
+    points.  libg4d_hip.so is loaded first -- such a library links against it and shares its error state.  Returns (CDLL, prototypes, constants)."""
+    if lib_path not in _more:
+        lib()
+        if not os.path.exists(lib_path):
+            raise G4DError(f"{lib_path} not found: the HIP extension is not built. Run `python -c 'import __graft_entry__ as g; g.build()'` "
+                           f"(or `make -C garment4d_amd/csrc`). There is no fallback path.")
+        try:
+            with open(header_path) as f:
+                protos, _, consts = parse_header(f.read())
+        except OSError as e:
+            raise G4DError(f"{header_path} cannot be read ({e.strerror}): the ctypes binding is derived from it. There is no fallback table.")
+        L = ctypes.CDLL(lib_path)
+        for name, (restype, argtypes) in protos.items():
+            fn = getattr(L, name)  # AttributeError if the library does not export a declared symbol
+            fn.argtypes = argtypes
+            fn.restype = restype
+        _more[lib_path] = (L, protos, consts)
+    return _more[lib_path]
+
+
+def render_lib():
+    """libg4d_render.so typed from include/g4d_render.h: (CDLL, prototypes, constants)."""
+    return load_pair(RENDER_HEADER_PATH, RENDER_LIB_PATH)
+
+
+def _entry(name):
+    """The loaded function behind an entry point's name: libg4d_hip.so's, or that of whichever further loaded library declares it."""
+    L = lib()
+    if name not in PROTOTYPES:
+        for M, protos, _ in _more.values():
+            if name in protos:
+                return getattr(M, name)
+    return getattr(L, name)
+
+
 _TRACE = os.environ.get("G4D_TRACE_CALLS", "0") != "0"   # debugging: every C-ABI call with its integer / float arguments on stderr
 _TIMED = None   # measurement: a list collecting (name, integer args, start event, end event) of every call (timed_calls)
 _UNTIMED = ("g4d_tuning_set", "g4d_tuning_set_thread", "g4d_launch_group_begin")   # host state only: nothing to put events around
@@ -166,6 +212,7 @@ class timed_calls:
 def call(name, *args):
     """Invoke a C-ABI entry point; non-zero status -> G4DError (the reference would exit(-1))."""
     L = lib()
+    fn = _entry(name)
     timed = _TIMED is not None and args and name not in _UNTIMED
     if _TRACE or timed:
         label, shown = name, tuple(a for a in args if isinstance(a, int) and not isinstance(a, bool) and abs(a) < (1 << 31))
@@ -183,11 +230,11 @@ def call(name, *args):
         import torch
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        rc = getattr(L, name)(*args)
+        rc = fn(*args)
         e1.record()
         _TIMED.append((label, shown, e0, e1))
     else:
-        rc = getattr(L, name)(*args)
+        rc = fn(*args)
     if rc != 0:
         raise G4DError(f"{name} failed with status {rc}: {L.g4d_last_error().decode(errors='replace')}")
     return rc
