@@ -9,7 +9,8 @@ are read from include/g4d.h when the library is loaded (`parse_header`), and tes
 gives -- a changed or new entry point shows up there as a changed or new line.
 
 Further libraries of the package are (header, library) pairs of the same shape, loaded by load_pair(): the rasterizer, include/g4d_render.h +
-lib/libg4d_render.so (render_lib(); record: tests/render_abi_snapshot.txt).  call() serves them too.
+lib/libg4d_render.so (render_lib(); record: tests/render_abi_snapshot.txt), and the virtual depth-sensor scans, include/g4d_scan.h +
+lib/libg4d_scan.so (scan_lib(); record: tests/scan_abi_snapshot.txt).  call() serves them too.
 """
 import ctypes
 import os
@@ -24,6 +25,9 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "g4d.h")
 # libg4d_hip.so and reports through the same g4d_last_error().  The names PROTOTYPES, SIGNATURES, RESTYPES, _lib, _header stay g4d.h's alone.
 RENDER_LIB_PATH = os.path.join(_HERE, "lib", "libg4d_render.so")
 RENDER_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "g4d_render.h")
+# the third pair, of the same shape: virtual depth-sensor scans (include/g4d_scan.h, libg4d_scan.so; scan_lib() loads it)
+SCAN_LIB_PATH = os.path.join(_HERE, "lib", "libg4d_scan.so")
+SCAN_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "g4d_scan.h")
 
 _lib = None
 _header = None   # HEADER_PATH once the names below are bound from it
@@ -170,6 +174,11 @@ def load_pair(header_path, lib_path):
 def render_lib():
     """libg4d_render.so typed from include/g4d_render.h: (CDLL, prototypes, constants)."""
     return load_pair(RENDER_HEADER_PATH, RENDER_LIB_PATH)
+
+
+def scan_lib():
+    """libg4d_scan.so typed from include/g4d_scan.h: (CDLL, prototypes, constants)."""
+    return load_pair(SCAN_HEADER_PATH, SCAN_LIB_PATH)
 
 
 def _entry(name):

@@ -81,16 +81,25 @@ class VertexJointSelector(nn.Module):
             self.tip_names = ["thumb", "index", "middle", "ring", "pinky"]
             idx += [vertex_ids[h + t] for h in ("l", "r") for t in self.tip_names]
         self.register_buffer("extra_joints_idxs", torch.tensor(idx, dtype=torch.long))
+        self._max_idx = max(idx) if idx else -1   # on the host: forward() compares it with the mesh size without a device round trip
 
     def forward(self, vertices, joints):
-        """joints (B,J,3) ++ vertices[:, extra] (B,E,3): the row gather runs on g4d_gather_rows_f32."""
+        """joints (B,J,3) ++ vertices[:, extra] (B,E,3): the row gather runs on g4d_gather_rows_f32, which takes its indices as they are.
+        The ids are SMPL's (up to 6787 of 6890 vertices); on a body with fewer vertices (the synthetic bodies) an id past the mesh has no
+        vertex: it is kept inside the buffer for the gather and its joint is NaN (the reference's index_select would raise)."""
         B, V, _ = vertices.shape
         E = self.extra_joints_idxs.numel()
         out = torch.empty((B, joints.shape[1] + E, 3), dtype=torch.float32, device=vertices.device)
         out[:, :joints.shape[1]] = joints
-        idx = self.extra_joints_idxs.to(torch.int32).expand(B, E).contiguous()
+        ids = self.extra_joints_idxs
+        if self._max_idx >= V:
+            ids = ids.clamp_max(max(V - 1, 0))
+        idx = ids.to(torch.int32).expand(B, E).contiguous()
         extra = torch.empty((B, E, 3), dtype=torch.float32, device=vertices.device)
-        _lib.call("g4d_gather_rows_f32", B, V, E, 3, vertices.contiguous().data_ptr(), idx.data_ptr(), extra.data_ptr(), _lib.stream_ptr())
+        if V > 0:
+            _lib.call("g4d_gather_rows_f32", B, V, E, 3, vertices.contiguous().data_ptr(), idx.data_ptr(), extra.data_ptr(), _lib.stream_ptr())
+        if self._max_idx >= V:
+            extra.masked_fill_((self.extra_joints_idxs >= V).view(1, E, 1), float("nan"))
         out[:, joints.shape[1]:] = extra
         return out
 
