@@ -19,6 +19,10 @@
 //     smallest index is found by bisection on the value (list in registers: compare + ballot + popcount per step, no LDS),
 //     the survivors are ranked (rank = number of smaller indices; LDS broadcast reads) and written straight to out[rank];
 //     padding = the rank-0 index, rows without a hit are zeros.
+//     Set form (g4d_ball_grid_query_set_f32, template flag SET): the same selection, but the kept hits leave in list order -- no rank pass
+//     (one LDS broadcast read + compare + add per PAIR of kept hits: ~100 VALU + 32 LDS instructions of a 32-sample list) -- for consumers
+//     that take a maximum over the neighbourhood, which depends on the SET of rows only; padding = slot 0, as the dead-tile rule of
+//     sa_table.hip and bench.py's live_rows_frac read it.
 //   dense ball (more than kCap = 512 hits: far more candidates than slots): the first nsample hits by index sit
 //     near the start of the cloud, so that (query, scale) falls back to the index-ordered scan with early exit -- the
 //     kernel never does worse than the scan it replaces.
@@ -27,6 +31,7 @@
 #include <cstdlib>
 
 #include "g4d_common.h"
+#include "../../include/g4d_sets.h"
 #include "ball_grid_build.h"
 
 namespace g4d {
@@ -48,7 +53,9 @@ __device__ __forceinline__ int query_cell(float v, float lo, float inv_c, int g)
     return (int)fminf(fmaxf(u, -2.f), (float)(g + 1));
 }
 
-template <int NS, int FM>
+// SET: the lists' consumer takes a maximum over the neighbourhood's rows, so only the SET of kept indices matters (and that the padding
+// repeats slot 0): the hits go out in list order, without the rank pass.  Which indices are kept is decided exactly as in the ordered form.
+template <int NS, int FM, bool SET>
 __global__ void __launch_bounds__(256) ball_grid_query_kernel(int n, int m, int qpw, const BgArgs a, const float *__restrict__ new_xyz_all,
                                                              const float *__restrict__ xyz_all, const unsigned char *__restrict__ ws_all,
                                                              size_t ws_stride, int cmax) {
@@ -169,6 +176,12 @@ __global__ void __launch_bounds__(256) ball_grid_query_kernel(int n, int m, int 
                             w += __builtin_popcountll(mask);
                         }
                     hacc = w;  // == ns
+                }
+                if constexpr (SET) {
+                    // set form: the kept indices in list order (hacc <= ns here: more hits than slots were cut to ns above), padding = slot 0
+                    const int first = L[0];
+                    for (int l = lane; l < ns; l += 64) out[l] = l < hacc ? L[l] : first;
+                    continue;
                 }
                 // rank = number of smaller indices (LDS broadcast reads), written straight to out[rank]
                 int first = 0;
@@ -342,13 +355,14 @@ int grid_build(int b, int n, float rmax, const float *xyz, void *ws, hipStream_t
 size_t grid_bytes_per_cloud(int n) { return grid_cloud_bytes(n); }
 size_t grid_records_offset(int n) { return kGridHdrBytes + ((((size_t)grid_cmax(n) + 1) * 4 + 63) & ~(size_t)63); }
 
-template <int NS, int FM>
+template <int NS, int FM, bool SET>
 static void grid_query_launch(dim3 grid, hipStream_t st, int n, int m, int qpw, const BgArgs &a, const float *new_xyz, const float *xyz,
                               const void *ws) {
-    hipLaunchKernelGGL((ball_grid_query_kernel<NS, FM>), grid, dim3(256), 0, st, n, m, qpw, a, new_xyz, xyz,
+    hipLaunchKernelGGL((ball_grid_query_kernel<NS, FM, SET>), grid, dim3(256), 0, st, n, m, qpw, a, new_xyz, xyz,
                        reinterpret_cast<const unsigned char *>(ws), grid_cloud_bytes(n), grid_cmax(n));
 }
 
+template <bool SET>
 static int grid_query(int b, int n, int m, int nscales, const float *radii, const int *nsamples, const float *new_xyz, const float *xyz,
                       int *const *idx, const void *ws, hipStream_t st) {
     BgArgs a = {};
@@ -364,12 +378,32 @@ static int grid_query(int b, int n, int m, int nscales, const float *radii, cons
     if (qpw_env > 0) qpw = qpw_env;
     dim3 grid((unsigned)((m + 4 * qpw - 1) / (4 * qpw)), (unsigned)b);
     G4D_WITH_FM(distance_contraction(), switch (nscales) {
-        case 1: grid_query_launch<1, FM>(grid, st, n, m, qpw, a, new_xyz, xyz, ws); break;
-        case 2: grid_query_launch<2, FM>(grid, st, n, m, qpw, a, new_xyz, xyz, ws); break;
-        case 3: grid_query_launch<3, FM>(grid, st, n, m, qpw, a, new_xyz, xyz, ws); break;
-        default: grid_query_launch<4, FM>(grid, st, n, m, qpw, a, new_xyz, xyz, ws); break;
+        case 1: grid_query_launch<1, FM, SET>(grid, st, n, m, qpw, a, new_xyz, xyz, ws); break;
+        case 2: grid_query_launch<2, FM, SET>(grid, st, n, m, qpw, a, new_xyz, xyz, ws); break;
+        case 3: grid_query_launch<3, FM, SET>(grid, st, n, m, qpw, a, new_xyz, xyz, ws); break;
+        default: grid_query_launch<4, FM, SET>(grid, st, n, m, qpw, a, new_xyz, xyz, ws); break;
     })
-    return check_launch("g4d_ball_grid_query_f32");
+    return check_launch(SET ? "g4d_ball_grid_query_set_f32" : "g4d_ball_grid_query_f32");
+}
+
+template <bool SET>
+static int grid_query_entry(const char *name, int b, int n, int m, int nscales, const float *radii, const int *nsamples, const float *new_xyz,
+                            const float *xyz, int *const *idx, const void *grid, float grid_rmax, g4d_stream_t stream) {
+    G4D_REQUIRE(b >= 0 && n >= 0 && m >= 0 && nscales >= 1 && nscales <= 4 && b <= 65535, "%s: bad sizes", name);
+    G4D_REQUIRE(radii && nsamples && idx, "%s: null pointer", name);
+    if (b == 0 || m == 0) return G4D_OK;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    for (int s = 0; s < nscales; ++s) {
+        G4D_REQUIRE(nsamples[s] > 0 && idx[s], "%s: bad scale %d", name, s);
+        G4D_REQUIRE(radii[s] <= grid_rmax, "%s: radius %g exceeds the radius the grid was built for (%g)", name, radii[s], grid_rmax);
+        if (n == 0) {
+            hipError_t e = hipMemsetAsync(idx[s], 0, sizeof(int) * (size_t)b * m * nsamples[s], st);
+            if (e != hipSuccess) return (int)e;
+        }
+    }
+    if (n == 0) return G4D_OK;
+    G4D_REQUIRE(new_xyz && xyz && grid, "%s: null pointer", name);
+    return grid_query<SET>(b, n, m, nscales, radii, nsamples, new_xyz, xyz, idx, grid, st);
 }
 
 }  // namespace g4d
@@ -390,22 +424,12 @@ extern "C" int g4d_ball_grid_build_f32(int b, int n, float rmax, const float *xy
 
 extern "C" int g4d_ball_grid_query_f32(int b, int n, int m, int nscales, const float *radii, const int *nsamples, const float *new_xyz,
                                        const float *xyz, int *const *idx, const void *grid, float grid_rmax, g4d_stream_t stream) {
-    using namespace g4d;
-    G4D_REQUIRE(b >= 0 && n >= 0 && m >= 0 && nscales >= 1 && nscales <= 4 && b <= 65535, "g4d_ball_grid_query_f32: bad sizes");
-    G4D_REQUIRE(radii && nsamples && idx, "g4d_ball_grid_query_f32: null pointer");
-    if (b == 0 || m == 0) return G4D_OK;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    for (int s = 0; s < nscales; ++s) {
-        G4D_REQUIRE(nsamples[s] > 0 && idx[s], "g4d_ball_grid_query_f32: bad scale %d", s);
-        G4D_REQUIRE(radii[s] <= grid_rmax, "g4d_ball_grid_query_f32: radius %g exceeds the radius the grid was built for (%g)", radii[s], grid_rmax);
-        if (n == 0) {
-            hipError_t e = hipMemsetAsync(idx[s], 0, sizeof(int) * (size_t)b * m * nsamples[s], st);
-            if (e != hipSuccess) return (int)e;
-        }
-    }
-    if (n == 0) return G4D_OK;
-    G4D_REQUIRE(new_xyz && xyz && grid, "g4d_ball_grid_query_f32: null pointer");
-    return grid_query(b, n, m, nscales, radii, nsamples, new_xyz, xyz, idx, grid, st);
+    return g4d::grid_query_entry<false>("g4d_ball_grid_query_f32", b, n, m, nscales, radii, nsamples, new_xyz, xyz, idx, grid, grid_rmax, stream);
+}
+
+extern "C" int g4d_ball_grid_query_set_f32(int b, int n, int m, int nscales, const float *radii, const int *nsamples, const float *new_xyz,
+                                           const float *xyz, int *const *idx, const void *grid, float grid_rmax, g4d_stream_t stream) {
+    return g4d::grid_query_entry<true>("g4d_ball_grid_query_set_f32", b, n, m, nscales, radii, nsamples, new_xyz, xyz, idx, grid, grid_rmax, stream);
 }
 
 extern "C" int g4d_ball_query_grid_f32(int b, int n, int m, int nscales, const float *radii, const int *nsamples, const float *new_xyz,

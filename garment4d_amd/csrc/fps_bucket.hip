@@ -2,8 +2,13 @@
 // N = 8192 (1.085 -> 0.84 us per round, B = 8) and the first FPS here whose work per round does not grow with N.
 //
 // In round j only points closer to the new sample than their current min-distance change, and every min-distance
-// is <= g_j, the value of the sample just selected (the global max).  The cloud is sorted along a Morton curve
-// (bitonic sort in LDS, once per launch) and cut into buckets of 64 consecutive points -- one VGPR "slot" of one
+// is <= g_j, the value of the sample just selected (the global max).  The cloud is ordered along a Morton curve
+// (once per launch: a counting sort in LDS on the coarse cell = the top 12 bits of the 30-bit Morton code -- histogram with LDS
+// atomics, exclusive scan, scatter; three passes where the exact bitonic sort of 64-bit keys it replaces took 91.  The place of
+// a point WITHIN its cell is the order in which the atomics retire and may differ from run to run; the outputs cannot: the
+// pruning below is exact for ANY composition of the buckets, and ties are decided on original indices, so samples, gathered
+// coordinates and scratch are the same whichever points share a bucket -- only the number of swept buckets depends on it, and
+// for that the buckets have to be compact, not exactly ordered) and cut into buckets of 64 consecutive points -- one VGPR "slot" of one
 // wave; a wave owns P CONSECUTIVE buckets of the Morton order, so the ~14 buckets a round touches sit in 2-3 waves and
 // the other waves only republish their cached candidate (dealing them round-robin makes ~14 waves pay the fixed
 // arg-max cost every round: 0.81 instead of 0.75 us per round).  Each wave keeps the boxes of its buckets lane-distributed.  A round is then
@@ -30,7 +35,9 @@
 
 namespace g4d {
 
-constexpr int kFpsHdr = 2048;   // LDS header in front of the sort keys / SoA cloud: exchange slots, candidate records, round results
+constexpr int kFpsHdr = 2048;   // LDS header in front of the sort arrays / SoA cloud: exchange slots, candidate records, round results
+constexpr int kFpsRecX = 256, kFpsRecV3 = kFpsRecX + 3 * 128;   // multi-pick rounds: the candidates' x | y | z arrays and the waves' third-best values (keys at 0)
+constexpr int kFpsCellBits = 12, kFpsCells = 1 << kFpsCellBits;   // coarse Morton cells of the counting sort (16 x 16 x 16 over the cloud's box)
 
 // --- pieces shared with fps.hip (kept local: both files are self-contained translation units)
 __device__ __forceinline__ unsigned fpsb_rank(int k, int bs, int log2bs) {
@@ -100,23 +107,25 @@ __device__ __forceinline__ unsigned part1by2(unsigned v) {  // spread the low 10
     return v;
 }
 
-// W waves, P buckets (slots) per wave; handles N <= 64*W*P points.  LDS: max(8*Npad sort keys, 12*N SoA) + 512.
+// W waves, P buckets (slots) per wave; handles N <= 64*W*P points.  LDS: header + max(4*(4096 + Npad) sort arrays, 12*N SoA) + the pick list.
 // KMAX > 1: the multi-pick round loop (below); KMAX = 1: one sample per round.
 // SOA: the LDS copy of the cloud (96 KB at n = 8192) that the winner's coordinates are read from.  SOA = false (multi-pick rounds only,
 // round 5): the coordinates come from the owning lane's REGISTERS -- the tie rank carries the slot number in its low bits, the wave's
 // best / second-best slot is a wave-uniform register index (s_set_gpr_idx_on + v_mov: the point arrays live in ONE 4 P-wide vector so
-// that the compiler indexes it instead of expanding a select chain), three v_readlane -- and the workgroup needs 70 KB of LDS (sort keys
-// + pick list) instead of 104: a 72 KB shared-MLP workgroup of another stream fits beside it on the same CU.
+// that the compiler indexes it instead of expanding a select chain), three v_readlane -- and the workgroup needs 54 KB of LDS (sort arrays
+// + pick list; 70 KB with the bitonic sort's 64-bit keys, until the counting sort) instead of 104: a 72 KB shared-MLP workgroup of another stream fits beside it on the same CU.
 template <int W, int P, int FM, int KMAX = 1, bool SOA = true>
 __device__ __forceinline__ void fps_bucket_body(int n, int m, int bs, int log2bs, int deal_kcap, int pick_off, const float *__restrict__ xyz_all,
                                                 float *__restrict__ temp_all, int *__restrict__ idx_all, float *__restrict__ nx_all, int cloud) {
-    constexpr int T = 64 * W, NPAD = T * P;
+    constexpr int T = 64 * W;   // (64 W P padded points: thread t holds points t + i T of the cloud's order during the sort, then slot i of its wave's buckets)
     static_assert(SOA || KMAX > 1, "the register form exists for the multi-pick loop only");
     constexpr int SB = SOA ? 0 : (P == 4 ? 2 : P == 8 ? 3 : P == 16 ? 4 : 5);   // slot bits below the tie rank (register form)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     unsigned long long *slots = reinterpret_cast<unsigned long long *>(smem_raw);         // [2][16] candidate keys
     float *red = reinterpret_cast<float *>(smem_raw + 256);                                // [6][16] bbox partials
-    unsigned long long *keys = reinterpret_cast<unsigned long long *>(smem_raw + kFpsHdr);   // [NPAD] during the sort
+    int *hist = reinterpret_cast<int *>(smem_raw + kFpsHdr);                               // [kFpsCells] during the sort: counts, then cell starts
+    int *order = hist + kFpsCells;                                                         // [NPAD] the points' indices in cell order (-1: padding)
+                                                                                           // (the launchers size the region: fps_bucket_body_bytes)
     float *sx = reinterpret_cast<float *>(smem_raw + kFpsHdr);                                // SoA cloud afterwards
     int *spick = reinterpret_cast<int *>(smem_raw + pick_off);                             // [m] the samples, written out once at the end
     float *sy = sx + n;
@@ -147,36 +156,66 @@ __device__ __forceinline__ void fps_bucket_body(int n, int m, int bs, int log2bs
         lx = fminf(lx, red[0 * 16 + w]); ly = fminf(ly, red[1 * 16 + w]); lz = fminf(lz, red[2 * 16 + w]);
         hx = fmaxf(hx, red[3 * 16 + w]); hy = fmaxf(hy, red[4 * 16 + w]); hz = fmaxf(hz, red[5 * 16 + w]);
     }
-    // the sort only has to be spatially coherent, not exact: any finite scale works (NaN/inf coordinates fall into cell 0)
+    // the order only has to be spatially coherent, not exact: any finite scale works (NaN/inf coordinates fall into cell 0)
     const float ext = fmaxf(fmaxf(hx - lx, hy - ly), fmaxf(hz - lz, 1e-30f));
     const float scale = 1023.0f / ext;
-    for (int q = t; q < NPAD; q += T) {
-        unsigned long long key = ~0ull;  // padding sorts to the end
+    // ---- B. counting sort on the coarse Morton cell (the top kFpsCellBits of the 30-bit code): histogram (the atomic's return value is the
+    //         point's place within its cell), exclusive scan, scatter of the point's index into order[] --------------------------------
+    for (int i = t; i < kFpsCells; i += T) hist[i] = 0;
+    __syncthreads();   // (also: everybody has read the bbox partials, whose space the scan's wave totals take)
+    int cp[P];         // cell | place << kFpsCellBits of point t + i T (place < 8192: 25 bits in all)
+#pragma unroll
+    for (int i = 0; i < P; ++i) {
+        const int q = t + i * T;
+        cp[i] = -1;
         if (q < n) {
             const float x = xyz[q * 3 + 0], y = xyz[q * 3 + 1], z = xyz[q * 3 + 2];
             const unsigned cx = (unsigned)fminf(fmaxf((x - lx) * scale, 0.f), 1023.f);
             const unsigned cy = (unsigned)fminf(fmaxf((y - ly) * scale, 0.f), 1023.f);
             const unsigned cz = (unsigned)fminf(fmaxf((z - lz) * scale, 0.f), 1023.f);
             const unsigned code = part1by2(cx) | (part1by2(cy) << 1) | (part1by2(cz) << 2);
-            key = ((unsigned long long)code << 32) | (unsigned)q;
+            const int cell = (int)(code >> (30 - kFpsCellBits));
+            cp[i] = cell | (atomicAdd(&hist[cell], 1) << kFpsCellBits);
+        } else {
+            order[q] = -1;   // padding: behind the n real points
         }
-        keys[q] = key;
     }
     __syncthreads();
-    // ---- B. bitonic sort of NPAD 64-bit keys in LDS ----------------------------------------------------------------
-    for (int k = 2; k <= NPAD; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = t; i < NPAD / 2; i += T) {
-                // i-th compare-exchange pair of this stage: lower index a with bit j clear
-                const int a = ((i & ~(j - 1)) << 1) | (i & (j - 1));
-                const int b2 = a | j;
-                const unsigned long long ka = keys[a], kb = keys[b2];
-                const bool asc = (a & k) == 0;
-                if ((ka > kb) == asc) { keys[a] = kb; keys[b2] = ka; }
-            }
-            __syncthreads();
+    {
+        constexpr int CH = kFpsCells / T;   // cells per thread (4 | 8 | 16)
+        static_assert(kFpsCells % T == 0 && CH % 4 == 0, "fps counting sort: whole int4 chunks per thread");
+        typedef int i32x4 __attribute__((ext_vector_type(4)));
+        i32x4 *h4 = reinterpret_cast<i32x4 *>(hist) + t * (CH / 4);
+        i32x4 hv[CH / 4];
+        int sum = 0;
+#pragma unroll
+        for (int i = 0; i < CH / 4; ++i) { hv[i] = h4[i]; sum += (hv[i].x + hv[i].y) + (hv[i].z + hv[i].w); }
+        int incl = sum;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int up = __shfl_up(incl, o);
+            if (lane >= o) incl += up;
+        }
+        int *wsum = reinterpret_cast<int *>(red);
+        if (lane == 63) wsum[wave] = incl;
+        __syncthreads();
+        int run = incl - sum;
+        for (int w = 0; w < wave; ++w) run += wsum[w];
+#pragma unroll
+        for (int i = 0; i < CH / 4; ++i) {
+            i32x4 o;
+            o.x = run; run += hv[i].x;
+            o.y = run; run += hv[i].y;
+            o.z = run; run += hv[i].z;
+            o.w = run; run += hv[i].w;
+            h4[i] = o;
         }
     }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < P; ++i)
+        if (cp[i] >= 0) order[hist[cp[i] & (kFpsCells - 1)] + (cp[i] >> kFpsCellBits)] = t + i * T;
+    __syncthreads();
     // ---- C. deal buckets of 64 sorted points to the waves, load the points into registers ----------------------------
     int pk[P];                     // original index of the slot's point (or -1)
     typedef float fvec __attribute__((ext_vector_type(4 * P)));
@@ -191,10 +230,9 @@ __device__ __forceinline__ void fps_bucket_body(int n, int m, int bs, int log2bs
         // ((i / deal) * W + w) * deal + i % deal.  deal = 1 spreads the ~14 buckets a round touches over ~14 waves (every one of
         // them pays the fixed arg-max cost), deal = P keeps them in 2-3 waves while the others republish their cached candidate
         const int q = (((i / deal) * W + wave) * deal + (i % deal)) * 64 + lane;
-        const unsigned long long key = keys[q];
-        pk[i] = (key == ~0ull) ? -1 : (int)(unsigned)key;
+        pk[i] = order[q];
     }
-    __syncthreads();  // everybody has read its keys: the region becomes the SoA cloud
+    __syncthreads();  // everybody has read its part of the order: the region becomes the SoA cloud
 #pragma unroll
     for (int i = 0; i < P; ++i) {
         const bool ok = pk[i] >= 0;
@@ -222,7 +260,7 @@ __device__ __forceinline__ void fps_bucket_body(int n, int m, int bs, int log2bs
         float *res0 = reinterpret_cast<float *>(smem_raw + 1024 + 256);
         res0[0] = x0; res0[1] = y0; res0[2] = z0; res0[3] = INF;
     }
-    // register form: the boxes wait in LDS (the sort keys are dead: everybody read its keys before the barrier above) and are re-read at the
+    // register form: the boxes wait in LDS (the sort arrays are dead: everybody read its part of the order before the barrier above) and are re-read at the
     // head of every round -- six registers that are NOT live while the top-two trees run (the kernel is held to 72 VGPRs -- 64 until round 6 -- so that a
     // 256-register shared-MLP wave of another stream shares the SIMD with four FPS waves); a bucket's box = 32 bytes, 8 distinct per wave
     float *sbox = reinterpret_cast<float *>(smem_raw + kFpsHdr) + (wave * P + (lane & (P - 1))) * 8;
@@ -233,9 +271,9 @@ __device__ __forceinline__ void fps_bucket_body(int n, int m, int bs, int log2bs
             *reinterpret_cast<f32x4b *>(sbox) = (f32x4b){blx, bly, blz, bhx};
             *reinterpret_cast<f32x2b *>(sbox + 4) = (f32x2b){bhy, bhz};
         }
-        if (lane < 2) {   // = rec[..]: "no candidate" until the wave's first sweep publishes one (third-best value: none)
-            slots[(wave * 2 + lane) * 4] = 0ull;
-            reinterpret_cast<float *>(smem_raw)[(wave * 2 + lane) * 8 + 5] = -2.f;
+        if (lane < 2) {   // = the wave's candidate records: "no candidate" until its first sweep publishes one (third-best value: none)
+            slots[wave * 2 + lane] = 0ull;
+            reinterpret_cast<float *>(smem_raw + kFpsRecV3)[wave] = -2.f;
         }
     }
     __syncthreads();
@@ -271,9 +309,13 @@ __device__ __forceinline__ void fps_bucket_body(int n, int m, int bs, int log2bs
         constexpr int NK = 2 * W;                            // keys per round (<= 32)
         const int KE = min(min(KE0, NK), max(1, kcap));      // run-time cap (tuning hook G4D_FPS_KCAP); never more than the keys a round has -- with
                                                              // W = 4 all 8 candidates can be clean, and nobody would have written samples 8 .. 15
-        static_assert(NK * 32 <= 1024 && 1024 + 256 + KE0 * 16 <= kFpsHdr, "fps multi-pick: the exchange areas must fit the LDS header");
-        static_assert(NK <= 64 && KE0 >= 1, "fps multi-pick: key / sample counts must fit a wave");
-        unsigned long long *rec = reinterpret_cast<unsigned long long *>(smem_raw);    // [2 W] candidate records of 32 bytes: key, x, y, z (the bbox partials are dead)
+        static_assert(NK <= 32 && 1024 + 256 + KE0 * 16 <= kFpsHdr, "fps multi-pick: the exchange areas must fit the LDS header");
+        static_assert(KE0 >= 1, "fps multi-pick: key / sample counts must fit a wave");
+        // the 2 W candidate records, one array per field (the bbox partials are dead): in step 5 lane jj reads field [jj], consecutive words of
+        // consecutive lanes -- as 32-byte structs lanes jj and jj + 8 met in one bank, a 4-way conflict on each of the five reads of every wave
+        unsigned long long *rkeys = reinterpret_cast<unsigned long long *>(smem_raw);   // [32] keys (0: none)
+        float *recx = reinterpret_cast<float *>(smem_raw + kFpsRecX), *recy = recx + 32, *recz = recy + 32;   // [32] each: the candidates' coordinates
+        float *recv3 = reinterpret_cast<float *>(smem_raw + kFpsRecV3);                 // [W] the waves' third-best values
         unsigned *nstop = reinterpret_cast<unsigned *>(smem_raw + 1024);                // [2] the round's length: LDS atomic min over the candidates' stop positions (two slots, alternating)
         float *res = reinterpret_cast<float *>(smem_raw + 1024 + 256);                  // [KE0] the round's samples in rank order: x, y, z, value
         const int ls = lane / P;                             // which sample of a pass this lane tests its box against
@@ -419,10 +461,9 @@ __device__ __forceinline__ void fps_bucket_body(int n, int m, int bs, int log2bs
                         const float bz1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(az1), h1)), bz2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(az2), h2));
                         rx = lane == 0 ? bx1 : bx2; ry = lane == 0 ? by1 : by2; rz = lane == 0 ? bz1 : bz2;
                         if (lane < 2) {   // publish here: the record doubles as the wave's cache
-                            typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
-                            *reinterpret_cast<u64x2 *>(&rec[(wave * 2 + lane) * 4]) = (u64x2){rkey, ((unsigned long long)__float_as_uint(ry) << 32) | __float_as_uint(rx)};
-                            typedef float f32x2b __attribute__((ext_vector_type(2)));
-                            *reinterpret_cast<f32x2b *>(reinterpret_cast<float *>(rec) + (wave * 2 + lane) * 8 + 4) = (f32x2b){rz, v3w};
+                            const int r_ = wave * 2 + lane;
+                            rkeys[r_] = rkey; recx[r_] = rx; recy[r_] = ry; recz[r_] = rz;
+                            if (lane == 0) recv3[wave] = v3w;
                         }
                     }
                 }
@@ -435,10 +476,9 @@ __device__ __forceinline__ void fps_bucket_body(int n, int m, int bs, int log2bs
 #endif
             // 4. publish the two candidates as records {key, x, y, z}; barrier A
             if (SOA && lane < 2) {
-                typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
-                typedef float f32x2b __attribute__((ext_vector_type(2)));
-                *reinterpret_cast<u64x2 *>(&rec[(wave * 2 + lane) * 4]) = (u64x2){rkey, ((unsigned long long)__float_as_uint(ry) << 32) | __float_as_uint(rx)};
-                *reinterpret_cast<f32x2b *>(reinterpret_cast<float *>(rec) + (wave * 2 + lane) * 8 + 4) = (f32x2b){rz, rv3};
+                const int r_ = wave * 2 + lane;
+                rkeys[r_] = rkey; recx[r_] = rx; recy[r_] = ry; recz[r_] = rz;
+                if (lane == 0) recv3[wave] = rv3;
             }
             __syncthreads();
 #ifdef G4D_FPS_DEBUG
@@ -451,12 +491,11 @@ __device__ __forceinline__ void fps_bucket_body(int n, int m, int bs, int log2bs
             //    candidate against ALL larger keys, so the flags of all candidates can be computed independently, here by 16 waves at once.
             {
                 const int c = lane >> 5, jj = lane & 31;
-                const float *recf = reinterpret_cast<const float *>(rec);
-                const unsigned long long kj = jj < NK ? rec[jj * 4] : 0ull;
-                const float jx = recf[jj * 8 + 2], jy = recf[jj * 8 + 3], jz = recf[jj * 8 + 4];
+                const unsigned long long kj = jj < NK ? rkeys[jj] : 0ull;
+                const float jx = recx[jj], jy = recy[jj], jz = recz[jj];
                 const int me = wave * 2 + c;
-                const unsigned long long km = rec[me * 4];
-                const float mx = recf[me * 8 + 2], my = recf[me * 8 + 3], mz = recf[me * 8 + 4];
+                const unsigned long long km = rkeys[me];
+                const float mx = recx[me], my = recy[me], mz = recz[me];
                 const float mv = __uint_as_float((unsigned)(km >> 32));
                 const bool gt = kj > km;   // (an empty slot has key 0: never larger; an empty OWN slot ranks behind every real key)
                 const bool aff = gt && !(dist2<FM>(mx - jx, my - jy, mz - jz) >= mv);
@@ -467,7 +506,7 @@ __device__ __forceinline__ void fps_bucket_body(int n, int m, int bs, int log2bs
                 // a wave publishes two keys, everything else it owns is at most its third-best value v3 (sent along with its records).  If BOTH
                 // keys of wave w rank above this candidate, one of w's hidden keys could rank above it too -- unless the candidate's value is
                 // strictly larger than v3(w).  Values only: a tie with v3 counts as "could" (safe).  A NaN fails `>`: stops, as everywhere.
-                const float v3j = recf[(jj >> 1) * 16 + 5];
+                const float v3j = recv3[min(jj >> 1, W - 1)];
                 const unsigned both = gth & (gth >> 1) & 0x55555555u;      // bit 2 w: keys 2 w and 2 w + 1 are both above this candidate
                 const bool hid = ((both >> (jj & ~1)) & 1u) != 0u && !(mv > v3j);
                 const unsigned long long hdm = __builtin_amdgcn_ballot_w64(hid);
@@ -706,12 +745,18 @@ fps_bucket_grid_reg_kernel(int b, int n, int m, int bs, int log2bs, int deal, in
     else ball_grid_build_body(n, cmax, cmax, cell_req, xyz_all, ws_all, ws_stride, (int)blockIdx.x - b);
 }
 
+// LDS behind the header: the counting sort's histogram + order array, later the SoA copy of the cloud (LDS-copy form)
+static size_t fps_bucket_body_bytes(size_t npad, int n, bool soa) {
+    const size_t sort = ((size_t)kFpsCells + npad) * 4;
+    return (!soa || sort > (size_t)n * 12) ? sort : (size_t)n * 12;
+}
+
 template <int W, int P, int FM>
 static int launch_bucket_fm(int b, int n, int m, int bs, int log2bs, const float *xyz, float *temp, int *idx, float *nx, hipStream_t s) {
     const size_t npad = (size_t)64 * W * P;
     const bool multi = fps_multi() > 1;
     const bool soa = !multi || fps_soa(b) || W != 16;   // (the register form is held to 72 VGPRs: 16 waves x 4 or 8 points per lane only)
-    const size_t body = (!soa || npad * 8 > (size_t)n * 12) ? npad * 8 : (size_t)n * 12;
+    const size_t body = fps_bucket_body_bytes(npad, n, soa);
     const size_t pick_off = (kFpsHdr + body + 15) & ~(size_t)15;
     const size_t lds = pick_off + (size_t)m * 4;
     if (lds > 160 * 1024 - 1024) return -1;   // the pick list lives in LDS: m beyond ~15.8k at n = 8192 goes to the next route (fps.hip)
@@ -739,7 +784,7 @@ int fps_bucket_grid_launch(int b, int n, int m, int bs, int log2bs, const float 
     const size_t npad = (size_t)64 * W * P;
     const bool multi = fps_multi() > 1;
     const bool soa = !multi || fps_soa(b);
-    const size_t body = (!soa || npad * 8 > (size_t)n * 12) ? npad * 8 : (size_t)n * 12;
+    const size_t body = fps_bucket_body_bytes(npad, n, soa);
     const size_t pick_off = (kFpsHdr + body + 15) & ~(size_t)15;
     const int cmax = grid_cmax(n);
     const size_t lds_fps = pick_off + (size_t)m * 4, lds_grid = ((size_t)cmax + 1) * 4 + 16 * 8 * 4;

@@ -454,6 +454,7 @@ def _run_stack(first_call, layers, rows, S, pool, out, col0, device):
 # (LANES_SORT -> tuning.Tuning.lanes_sort)
 # (COHERENT_LANES -> tuning.Tuning.coherent_lanes)
 # (GRID_MIN_N -> tuning.Tuning.grid_min_n) clouds at least this large go through the cell grid (csrc/ball_grid.hip)
+# (tuning.Tuning.bq_set) max-pooled SA levels take the grid query's lists as sets (no rank pass; A/B switch)
 
 
 def build_ball_grid(xyz, rmax):
@@ -466,11 +467,13 @@ def build_ball_grid(xyz, rmax):
     return ws, float(rmax)
 
 
-def ball_query_msg(radii, nsamples, xyz, new_xyz, coherent=False, grid=None):
+def ball_query_msg(radii, nsamples, xyz, new_xyz, coherent=False, grid=None, set_form=False):
     """All scales of an MSG layer in one pass over the cloud; returns one (B,P,nsample) int32 tensor per scale.
     coherent=True: the cloud's index order is spatially coherent (mesh vertices) -> block-bounds skipping (same results).
     grid: None = automatic (cell grid for clouds of >= Tuning.grid_min_n points), False = scan, True = build a grid, or a
-    (workspace, rmax) pair from build_ball_grid.  Every route returns the same indices, bit for bit."""
+    (workspace, rmax) pair from build_ball_grid.  Every route returns the same indices, bit for bit.
+    set_form=True (for callers that max-pool over the lists and show them to nobody): the grid route may return each list as a SET -- the same
+    indices, each once, in unspecified order, padding = slot 0 (g4d_ball_grid_query_set_f32: no rank pass); the other routes are unaffected."""
     B, N, _ = xyz.shape
     P = new_xyz.shape[1]
     outs = [torch.empty((B, P, ns), dtype=torch.int32, device=xyz.device) for ns in nsamples]
@@ -483,7 +486,9 @@ def ball_query_msg(radii, nsamples, xyz, new_xyz, coherent=False, grid=None):
         n = min(4, len(radii) - done)
         R, NS, IP = _floats(radii[done:done + n]), _ints(nsamples[done:done + n]), _ptrs(outs[done:done + n])
         if grid:
-            _lib.call("g4d_ball_grid_query_f32", B, N, P, n, R, NS, new_xyz.data_ptr(), xyz.data_ptr(), IP, grid[0].data_ptr(), grid[1], _lib.stream_ptr())
+            if set_form:
+                _lib.sets_lib()   # (the set form is declared in include/g4d_sets.h)
+            _lib.call("g4d_ball_grid_query_set_f32" if set_form else "g4d_ball_grid_query_f32", B, N, P, n, R, NS, new_xyz.data_ptr(), xyz.data_ptr(), IP, grid[0].data_ptr(), grid[1], _lib.stream_ptr())
         elif coherent and N >= 256:
             boxes = torch.empty((B, (N + 15) // 16, 6), dtype=torch.float32, device=xyz.device)   # 16-point sub-block bounds
             if _T().coherent_lanes:   # one lane per query; the queries are cell-sorted first so that a wave's 64 are compact
@@ -772,7 +777,10 @@ def sa_forward(sa, xyz, feats_pm=None, new_xyz=None, grid=None, idxs=None):
         out = torch.empty((B, P, ctot), dtype=torch.float32, device=xyz.device)
         col0 = 0
         if idxs is None:   # (else: the caller's ball_query_msg / ball_query_msg2 result for exactly these centroids)
-            idxs = ball_query_msg([g.radius for g in sa.groupers], [g.nsample for g in sa.groupers], xyz, new_xyz, grid=grid)
+            # the lists stay in this function, and a maximum over a neighbourhood's rows depends on the set of indices only (an average's
+            # rounding depends on their order: it keeps the ordered lists)
+            idxs = ball_query_msg([g.radius for g in sa.groupers], [g.nsample for g in sa.groupers], xyz, new_xyz, grid=grid,
+                                  set_form=pool == 1 and _T().bq_set)
         if (_T().use_sa_xyz and _T().sa_xyz_pair and C == 0 and len(packed) == 2 and current_precision() == "fp32" and B * N * 12 < 2 ** 32
                 and all(int(g.use_xyz) for g in sa.groupers) and all(len(L_) == 3 and all(L.relu for L in L_) for L_ in packed)
                 and [L.Cout for L in packed[0]] == [16, 16, 32] and [L.Cout for L in packed[1]] == [32, 32, 64]

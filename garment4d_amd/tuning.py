@@ -56,6 +56,7 @@ class Tuning:
     lanes_sort: bool = False           # lanes-kernel ball query over cell-sorted queries
     coherent_lanes: bool = False       # lanes-kernel ball query for coherent clouds
     grid_min_n: int = 4096             # clouds at least this large go through the cell grid (csrc/ball_grid.hip)
+    bq_set: bool = True                # grid ball query feeding a max-pooled fused SA level: set-form lists (g4d_ball_grid_query_set_f32, no rank pass)
     fps_pair: bool = True              # two consecutive small FPS levels in one launch
     bq_multi: bool = True              # the ball queries of two small SA levels in one launch
     search_multi: bool = True          # the inner levels' ball queries AND three-NN searches in one launch
@@ -132,7 +133,7 @@ def from_environment() -> Tuning:
         use_wave=_env_flag("G4D_MLP_WAVE", d.use_wave), use_chain=_env_flag("G4D_MLP_CHAIN", d.use_chain), stream_gemm=_env_flag("G4D_GEMM_STREAM", d.stream_gemm),
         bf16_min_rows=_env_int("G4D_BF16_MIN_ROWS", d.bf16_min_rows), overlap_sampling=_env_flag("G4D_OVERLAP_SAMPLING", d.overlap_sampling),
         lanes_sort=_env_flag("G4D_BQ_LANES_SORT", d.lanes_sort), coherent_lanes=_env_flag("G4D_BQ_LANES", d.coherent_lanes),
-        grid_min_n=_env_int("G4D_BQ_GRID_MIN_N", d.grid_min_n), fps_pair=_env_flag("G4D_FPS_PAIR", d.fps_pair), bq_multi=_env_flag("G4D_BQ_MULTI", d.bq_multi),
+        grid_min_n=_env_int("G4D_BQ_GRID_MIN_N", d.grid_min_n), bq_set=_env_flag("G4D_BQ_SET", d.bq_set), fps_pair=_env_flag("G4D_FPS_PAIR", d.fps_pair), bq_multi=_env_flag("G4D_BQ_MULTI", d.bq_multi),
         search_multi=_env_flag("G4D_SEARCH_MULTI", d.search_multi), three_nn_grid_min_m=_env_int("G4D_NN_GRID_MIN_M", d.three_nn_grid_min_m),
         nn_cells=_env_flag("G4D_NN_CELLS", d.nn_cells), nn_multi=_env_flag("G4D_NN_MULTI", d.nn_multi), nn_prune=_env_flag("G4D_NN_PRUNE", d.nn_prune), sa_xyz_pair=_env_flag("G4D_SA_XYZ_PAIR", d.sa_xyz_pair),
         use_sa_xyz=_env_flag("G4D_SA_XYZ", d.use_sa_xyz), sa_xyz_table=_env_flag("G4D_SA_XYZ_TABLE", d.sa_xyz_table), sa_table=_env_flag("G4D_SA_TABLE", d.sa_table),
