@@ -10,7 +10,8 @@ gives -- a changed or new entry point shows up there as a changed or new line.
 
 Further libraries of the package are (header, library) pairs of the same shape, loaded by load_pair(): the rasterizer, include/g4d_render.h +
 lib/libg4d_render.so (render_lib(); record: tests/render_abi_snapshot.txt), and the virtual depth-sensor scans, include/g4d_scan.h +
-lib/libg4d_scan.so (scan_lib(); record: tests/scan_abi_snapshot.txt).  call() serves them too.  include/g4d_sets.h is a further header of
+lib/libg4d_scan.so (scan_lib(); record: tests/scan_abi_snapshot.txt), and the point-to-surface loss, include/g4d_fit.h + lib/libg4d_fit.so
+(fit_lib(); record: tests/fit_abi_snapshot.txt).  call() serves them too.  include/g4d_sets.h is a further header of
 libg4d_hip.so ITSELF (sets_lib(); record: tests/sets_abi_snapshot.txt): entry points added after g4d.h's record was closed.
 """
 import ctypes
@@ -29,6 +30,9 @@ RENDER_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "g4d_render
 # the third pair, of the same shape: virtual depth-sensor scans (include/g4d_scan.h, libg4d_scan.so; scan_lib() loads it)
 SCAN_LIB_PATH = os.path.join(_HERE, "lib", "libg4d_scan.so")
 SCAN_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "g4d_scan.h")
+# the fourth pair: point-to-surface loss and its gradient (include/g4d_fit.h, libg4d_fit.so; fit_lib() loads it)
+FIT_LIB_PATH = os.path.join(_HERE, "lib", "libg4d_fit.so")
+FIT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "g4d_fit.h")
 
 # a further header of libg4d_hip.so itself (no library of its own): entry points that came after the record of g4d.h (sets_lib() binds them)
 SETS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "g4d_sets.h")
@@ -183,6 +187,11 @@ def render_lib():
 def scan_lib():
     """libg4d_scan.so typed from include/g4d_scan.h: (CDLL, prototypes, constants)."""
     return load_pair(SCAN_HEADER_PATH, SCAN_LIB_PATH)
+
+
+def fit_lib():
+    """libg4d_fit.so typed from include/g4d_fit.h: (CDLL, prototypes, constants)."""
+    return load_pair(FIT_HEADER_PATH, FIT_LIB_PATH)
 
 
 def sets_lib():
