@@ -32,17 +32,6 @@ __device__ __forceinline__ int cell_of(float v, float lo, float inv_c, int g) {
     return (int)u;
 }
 
-__device__ __forceinline__ float wave_min_all(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ float wave_max_all(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
-
 __device__ __forceinline__ void ball_grid_build_body(int n, int cmax, int budget, float cell_req, const float *__restrict__ xyz_all,
                                                      unsigned char *__restrict__ ws_all, size_t ws_stride, int cloud) {
     extern __shared__ __attribute__((aligned(16))) int hist[];  // [cmax + 1], then 16 x 8 floats of reduction scratch

@@ -496,7 +496,7 @@ static int ball_query_msg_impl(int b, int n, int m, int nscales, const float *ra
     if (n == 0) return G4D_OK;
     // queries per wave: keep >= ~4096 waves in the launch when the problem allows
     const long long queries = (long long)b * m;
-    static const long long min_waves = getenv("G4D_BQ_MIN_WAVES") ? atoll(getenv("G4D_BQ_MIN_WAVES")) : 4096;  // measured: SA1 (8192 queries) 55 us at 4 queries per wave, 44 at 2, 58 at 1
+    static const long long min_waves = env_ll("G4D_BQ_MIN_WAVES", 4096);  // measured: SA1 (8192 queries) 55 us at 4 queries per wave, 44 at 2, 58 at 1
     int qw = 4;
     while (qw > 1 && queries / qw < min_waves) qw >>= 1;
     dim3 grid((m + 4 * qw - 1) / (4 * qw), b);
@@ -659,7 +659,7 @@ extern "C" int g4d_search_multi_f32(int b, int nscales, int n0, int m0, const fl
         nq.blk_end[i] = nblocks;
     }
     nq.count = nn_count;
-    static const int qw_env = getenv("G4D_SEARCH_MULTI_QW") ? atoi(getenv("G4D_SEARCH_MULTI_QW")) : 0;   // tuning hook: 1 | 4
+    static const int qw_env = env_int("G4D_SEARCH_MULTI_QW", 0);   // tuning hook: 1 | 4
     const int qw = qw_env == 1 || qw_env == 4 ? qw_env : ((long long)b * (m0 + m1) >= 32768 ? 4 : 1);
     q.blk0 = (m0 + 4 * qw - 1) / (4 * qw);
     const int bq_blocks = q.blk0 + (m1 + 4 * qw - 1) / (4 * qw);

@@ -160,11 +160,10 @@ __global__ void __launch_bounds__(256, 2) fp_init_kernel(const FpInitArgs a) {
         return r;
     };
     struct Ctx { float w0, w1, w2; unsigned k0, k1, k2; };
-    auto make = [&](int tile, const Raw &r) {   // pointnet2_utils.py:98 sqrt; pointnet2_modules.py:140-142 inverse-distance weights
+    auto make = [&](int tile, const Raw &r) {   // interpolation weights and the rows' offsets in the table
         Ctx c;
-        const float r0 = 1.0f / (__fsqrt_rn(r.d0) + 1e-8f), r1 = 1.0f / (__fsqrt_rn(r.d1) + 1e-8f), r2 = 1.0f / (__fsqrt_rn(r.d2) + 1e-8f);
-        const float norm = (r0 + r1) + r2;
-        c.w0 = r0 / norm; c.w1 = r1 / norm; c.w2 = r2 / norm;
+        const InterpW w = interp_weights(r.d0, r.d1, r.d2);
+        c.w0 = w.w0; c.w1 = w.w1; c.w2 = w.w2;
         const int row = min(tile * 16 + fi, a.rows - 1);
         const int b0 = __builtin_amdgcn_readfirstlane((tile * 16) / a.n);   // a tile touches at most two clouds (n >= 16)
         const unsigned base = (unsigned)(b0 + (row >= (b0 + 1) * a.n ? 1 : 0)) * (unsigned)a.m;
@@ -370,13 +369,7 @@ int g4d::fp_init_try(const StackCall &c, hipStream_t st) {
     a.out = in.out; a.ldo = in.ldo; a.tap = c.tap_out; a.tap_ld = c.tap_ld;
     static unsigned long long attr = 0;
     if (const int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(fp_init_kernel), kStageBytes, attr, "g4d_fp_init")) return rc;
-    static const int resident = [] {
-        int per_cu = 0, dev = 0;
-        hipDeviceProp_t prop;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fp_init_kernel, 256, kStageBytes) != hipSuccess || per_cu < 1) per_cu = 1;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess || prop.multiProcessorCount < 1) return per_cu * 256;
-        return per_cu * prop.multiProcessorCount;
-    }();
+    static const int resident = resident_workgroups(fp_init_kernel, 256, kStageBytes);
     const long long want = ((c.rows + 15) / 16 + 3) / 4;
     hipLaunchKernelGGL(fp_init_kernel, dim3((unsigned)(want < resident ? want : resident)), dim3(256), kStageBytes, st, a);
     return check_launch("g4d_fp_init");

@@ -87,13 +87,12 @@ __global__ void __launch_bounds__(256, kD <= 4 ? 3 : 2) fp_table_head_kernel(con
         if constexpr (PERM) r.orow = b * a.n + reinterpret_cast<const int *>(a.perm_rec + (size_t)b * a.perm_stride)[4 * (row - b * a.n) + 3];
         return r;
     };
-    // level 2: interpolation weights (pointnet2_utils.py:98 sqrt; pointnet2_modules.py:140-142) and the rows' offsets in the table
+    // level 2: interpolation weights (interp_weights) and the rows' offsets in the table
     struct Ctx { float w0, w1, w2; unsigned k0, k1, k2; int orow; };
     auto make = [&](int tile, const Raw &r) {
         Ctx c;
-        const float r0 = 1.0f / (__fsqrt_rn(r.d0) + 1e-8f), r1 = 1.0f / (__fsqrt_rn(r.d1) + 1e-8f), r2 = 1.0f / (__fsqrt_rn(r.d2) + 1e-8f);
-        const float norm = (r0 + r1) + r2;
-        c.w0 = r0 / norm; c.w1 = r1 / norm; c.w2 = r2 / norm;
+        const InterpW w = interp_weights(r.d0, r.d1, r.d2);
+        c.w0 = w.w0; c.w1 = w.w1; c.w2 = w.w2;
         const int row = min(tile * 16 + fi, a.rows - 1);
         const int b0 = __builtin_amdgcn_readfirstlane((tile * 16) / a.n);
         const unsigned base = (unsigned)(b0 + (row >= (b0 + 1) * a.n ? 1 : 0)) * (unsigned)a.m;
@@ -240,12 +239,7 @@ int g4d::fp_table_try(const StackCall &c, hipStream_t st) {
                             : (perm_rec ? fp_table_head_kernel<true, 2, true> : fp_table_head_kernel<false, 2, true>);
     static int resident[4] = {0, 0, 0, 0};
     int &res = resident[(perm_rec ? 1 : 0) + (alone ? 2 : 0)];
-    if (res == 0) {   // (benign race: every thread computes the same value)
-        int per_cu = 0, dev = 0;
-        hipDeviceProp_t prop;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 256, 0) != hipSuccess || per_cu < 1) per_cu = 1;
-        res = (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess || prop.multiProcessorCount < 1) ? per_cu * 256 : per_cu * prop.multiProcessorCount;
-    }
+    if (res == 0) res = resident_workgroups(kern, 256, 0);   // (benign race: every thread computes the same value)
     const long long want = ((c.rows + 15) / 16 + 3) / 4;
     hipLaunchKernelGGL(kern, dim3((unsigned)(want < res ? want : res)), dim3(256), 0, st, a);
     return check_launch("g4d_fp_table_head");

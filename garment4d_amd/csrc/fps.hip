@@ -31,46 +31,12 @@ __device__ __host__ constexpr int brev_small(int v) {
     return r;
 }
 
-// fminf() makes hipcc canonicalise the loop-carried operand (an extra v_max x,x per point); the bare
-// instruction has the semantics wanted here (IEEE mode: a NaN operand yields the other operand).
-__device__ __forceinline__ float min_f32(float a, float b) {
-    float r;
-    asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-
 struct FpsCand {  // one wave's candidate for this round
     float val;
-    unsigned rank;  // (bitrev(k mod bs) << 16) | (k / bs): smaller wins among equal val
+    unsigned rank;  // fps_rank(k): smaller wins among equal val
     int k;
     int pad;
 };
-
-__device__ __forceinline__ unsigned fps_rank(int k, int bs, int log2bs) {
-    const unsigned c = (unsigned)k & (unsigned)(bs - 1);
-    const unsigned q = (unsigned)k >> log2bs;
-    const unsigned br = log2bs ? (__builtin_bitreverse32(c) >> (32 - log2bs)) : 0u;
-    return (br << 16) | q;
-}
-
-// max of W (4/8/16) 64-bit keys held by lanes 0..W-1 of each 16-lane row (Hillis-Steele with row_shr; lanes
-// without a source read 0, which never wins).  Result valid in lane W-1.
-template <int W>
-__device__ __forceinline__ unsigned long long row_max_u64(unsigned long long key) {
-#define G4D_STEP(CTRL)                                                                                       \
-    {                                                                                                        \
-        const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)key, CTRL, 0xf, 0xf, true);        \
-        const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(key >> 32), CTRL, 0xf, 0xf, true); \
-        const unsigned long long o = ((unsigned long long)hi << 32) | lo;                                    \
-        key = o > key ? o : key;                                                                             \
-    }
-    G4D_STEP(0x111)
-    G4D_STEP(0x112)
-    if constexpr (W >= 8) G4D_STEP(0x114)
-    if constexpr (W >= 16) G4D_STEP(0x118)
-#undef G4D_STEP
-    return key;
-}
 
 // Wave arg-max under (value desc, rank asc).  `best` per lane, `k` per lane.  Returns uniform results.
 __device__ __forceinline__ void wave_argmax(float best, int k, int bs, int log2bs, float &wval, int &wk, unsigned &wrank) {
@@ -130,7 +96,7 @@ __global__ void __launch_bounds__(64 * W) fps_reg_kernel(int n, int m, int bs, i
         for (int i = 0; i < P; ++i) {
             const float dx = px[i] - x1, dy = py[i] - y1, dz = pz[i] - z1;
             const float d = dist2<FM>(dx, dy, dz);
-            const float d2 = min_f32(d, md[i]);
+            const float d2 = bare_min_f32(d, md[i]);
             md[i] = d2;
             const bool gt = d2 > best;
             bslot = gt ? i : bslot;
@@ -216,7 +182,7 @@ __global__ void __launch_bounds__(256) fps_reg_pair_kernel(int m2, const float *
             for (int i = 0; i < UA; ++i) {
                 const float dx = px[i] - x1, dy = py[i] - y1, dz = pz[i] - z1;
                 const float d = dist2<FM>(dx, dy, dz);
-                const float d2 = min_f32(d, md[i]);
+                const float d2 = bare_min_f32(d, md[i]);
                 md[i] = d2;
                 const bool gt = d2 > best;
                 bslot = gt ? i : bslot;
@@ -266,7 +232,7 @@ __global__ void __launch_bounds__(256) fps_reg_pair_kernel(int m2, const float *
             for (int i = 0; i < UB; ++i) {
                 const float dx = px[i] - x1, dy = py[i] - y1, dz = pz[i] - z1;
                 const float d = dist2<FM>(dx, dy, dz);
-                const float d2 = min_f32(d, md[i]);
+                const float d2 = bare_min_f32(d, md[i]);
                 md[i] = d2;
                 const bool gt = d2 > best;
                 bslot = gt ? i : bslot;
@@ -363,6 +329,11 @@ static int ref_block_size(int work_size) {
     if (v < 1) v = 1;
     return v;
 }
+static int ref_block_log2(int bs) {   // bs = ref_block_size(n) and its log2: what the tie rank (fps_rank) is made of
+    int log2bs = 0;
+    while ((1 << log2bs) < bs) ++log2bs;
+    return log2bs;
+}
 
 template <int W, int U, int Q, int FM>
 static int launch_reg_fm(int b, int n, int m, int bs, int log2bs, const float *xyz, float *temp, int *idx, float *nx, hipStream_t s) {
@@ -396,24 +367,22 @@ static int fps_impl(int b, int n, int m, const float *xyz, float *temp, int *idx
     G4D_REQUIRE(n > 0, "g4d_fps_f32: n must be > 0 when m > 0");
     G4D_REQUIRE(xyz && idx, "g4d_fps_f32: null pointer");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const int bs = ref_block_size(n);
-    int log2bs = 0;
-    while ((1 << log2bs) < bs) ++log2bs;
-    const int q = (n + bs - 1) / bs;
+    const int bs = ref_block_size(n), log2bs = ref_block_log2(bs);
+    const int q =(n + bs - 1) / bs;
     if (g_fps_force_w < 0) {
         const char *e = getenv("G4D_FPS_W");
         g_fps_force_w = e ? atoi(e) : 99;
     }
     const int force = g_fps_force_w;
     // 4096 < n <= 8192: bucketed kernel with exact box pruning (fps_bucket.hip); G4D_FPS_BUCKET=0 turns it off
-    static const int use_bucket = getenv("G4D_FPS_BUCKET") ? atoi(getenv("G4D_FPS_BUCKET")) : 1;  // 0 = off, 2 = also 2048 < n <= 4096
+    static const int use_bucket = env_int("G4D_FPS_BUCKET", 1);  // 0 = off, 2 = also 2048 < n <= 4096
     if (use_bucket && force > 16 && n > (use_bucket >= 2 ? 2048 : 4096) && n <= 8192) {
         const int rc = fps_bucket_dispatch(b, n, m, bs, log2bs, xyz, temp, idx, nx, s);
         if (rc >= 0) return rc;
     }
     // 8192 < n <= 32768: the large-cloud bucketed kernel (fps_big.hip: min-distances in registers, coordinates from L2).  The
     // register-resident kernel below still takes 8192 < n <= 12800 when cloud + pick list fit LDS (G4D_FPS_BIG=2 sends those here too).
-    static const int use_big = getenv("G4D_FPS_BIG") ? atoi(getenv("G4D_FPS_BIG")) : 1;
+    static const int use_big = env_int("G4D_FPS_BIG", 1);
     const bool lds_ok = (size_t)n * 12 + (size_t)m * 4 + 512 <= 158 * 1024;   // SoA cloud + the pick list
     if (use_big && force > 16 && n > 8192 && n <= 32768 && (use_big >= 2 || !(lds_ok && n <= 12800))) {
         const int rc = fps_big_dispatch(b, n, m, bs, log2bs, xyz, temp, idx, nx, s);
@@ -512,13 +481,11 @@ extern "C" int g4d_fps_gather_grid_f32(int b, int n, int m, const float *xyz, in
     G4D_REQUIRE(b >= 0 && n > 0 && m > 0 && rmax > 0.f, "g4d_fps_gather_grid_f32: bad sizes");
     if (b == 0) return G4D_OK;
     G4D_REQUIRE(xyz && idx && new_xyz && grid, "g4d_fps_gather_grid_f32: null pointer");
-    static const int merged = getenv("G4D_FPS_GRID_MERGED") ? atoi(getenv("G4D_FPS_GRID_MERGED")) : 1;
-    static const int use_bucket = getenv("G4D_FPS_BUCKET") ? atoi(getenv("G4D_FPS_BUCKET")) : 1;
+    static const int merged = env_int("G4D_FPS_GRID_MERGED", 1);
+    static const int use_bucket = env_int("G4D_FPS_BUCKET", 1);
     if (merged && use_bucket && !getenv("G4D_FPS_W") && !getenv("G4D_FPS_BUCKET_W") && !getenv("G4D_FPS_DEAL")) {
-        const int bs = ref_block_size(n);
-        int log2bs = 0;
-        while ((1 << log2bs) < bs) ++log2bs;
-        const int rc = fps_bucket_grid_launch(b, n, m, bs, log2bs, xyz, idx, new_xyz, rmax, grid, reinterpret_cast<hipStream_t>(stream));
+        const int bs = ref_block_size(n), log2bs = ref_block_log2(bs);
+        const int rc =fps_bucket_grid_launch(b, n, m, bs, log2bs, xyz, idx, new_xyz, rmax, grid, reinterpret_cast<hipStream_t>(stream));
         if (rc >= 0) return rc;
     }
     if (const int rc = g4d_fps_gather_f32(b, n, m, xyz, nullptr, idx, new_xyz, stream)) return rc;

@@ -22,52 +22,13 @@ namespace g4d {
 
 constexpr int kBigHdr = 2048;
 
-__device__ __forceinline__ unsigned fpsg_rank(int k, int bs, int log2bs) {
-    const unsigned c = (unsigned)k & (unsigned)(bs - 1);
-    const unsigned q = (unsigned)k >> log2bs;
-    const unsigned br = log2bs ? (__builtin_bitreverse32(c) >> (32 - log2bs)) : 0u;
-    return (br << 16) | q;
-}
-__device__ __forceinline__ int fpsg_index(unsigned rank, int log2bs) {   // inverse of fpsg_rank
+__device__ __forceinline__ int fpsg_index(unsigned rank, int log2bs) {   // inverse of fps_rank
     const unsigned c = log2bs ? (__builtin_bitreverse32(rank >> 16) >> (32 - log2bs)) : 0u;
     return (int)(((rank & 0xffffu) << log2bs) | c);
 }
-__device__ __forceinline__ float fpsg_min(float a, float b) {
-    float r;
-    asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ float fpsg_max(float a, float b) {  // bare v_max_f32 (inputs are never NaN)
-    float r;
-    asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ float fpsg_wave_min(float v) {
-    int out;
-    asm volatile(
-        "s_nop 1\n\tv_min_f32_dpp %0, %0, %0 row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 1\n\tv_min_f32_dpp %0, %0, %0 row_shr:2 row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 1\n\tv_min_f32_dpp %0, %0, %0 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 1\n\tv_min_f32_dpp %0, %0, %0 row_shr:8 row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 1\n\tv_min_f32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
-        "s_nop 1\n\tv_min_f32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf\n\t"
-        "s_nop 1\n\tv_readlane_b32 %1, %0, 63\n\ts_nop 3"
-        : "+v"(v), "=s"(out));
-    return __int_as_float(out);
-}
-__device__ __forceinline__ unsigned fpsg_part1by2(unsigned v) {
-    v &= 0x3ffu;
-    v = (v | (v << 16)) & 0x030000ffu;
-    v = (v | (v << 8)) & 0x0300f00fu;
-    v = (v | (v << 4)) & 0x030c30c3u;
-    v = (v | (v << 2)) & 0x09249249u;
-    return v;
-}
-// 15-bit tie rank of point k when bs = 1024 (every n > 1024): (bit-reversed (k mod 1024)) << 5 | k / 1024 -- the order of fpsg_rank, k < 32768
+// 15-bit tie rank of point k when bs = 1024 (every n > 1024): (bit-reversed (k mod 1024)) << 5 | k / 1024 -- the order of fps_rank, k < 32768
 __device__ __forceinline__ unsigned fpsg_rank16(int k) { return ((__builtin_bitreverse32((unsigned)k & 1023u) >> 22) << 5) | ((unsigned)k >> 10); }
 __device__ __forceinline__ int fpsg_index16(unsigned r16) { return (int)(((r16 & 31u) << 10) | (__builtin_bitreverse32(r16 >> 5) >> 22)); }
-struct __attribute__((packed, aligned(4))) F3g { float x, y, z; };
-__device__ __forceinline__ F3g fpsg_ld3(const float *base, int k) { return *reinterpret_cast<const F3g *>(base + (size_t)k * 3); }
 
 // W = 16 waves, P slots per lane (16 | 32): N <= 1024 P.  LDS: header + 4 * 1024 P sort keys (the pick list reuses that region).
 // MULTI (round 6): multi-pick rounds as in fps_bucket.hip -- every wave publishes its two best keys and its third-best VALUE, one pass of pair tests
@@ -93,11 +54,11 @@ __global__ void __launch_bounds__(1024) fps_big_kernel(int n, int m, int bs, int
     // ---- A. bounding box, Morton keys -------------------------------------------------------------------------------------------
     float lx = INF, ly = INF, lz = INF, hx = -INF, hy = -INF, hz = -INF;
     for (int k = t; k < n; k += T) {
-        const F3g p = fpsg_ld3(xyz, k);
+        const F3 p = ld_point(xyz, k);
         lx = fminf(lx, p.x); ly = fminf(ly, p.y); lz = fminf(lz, p.z);
         hx = fmaxf(hx, p.x); hy = fmaxf(hy, p.y); hz = fmaxf(hz, p.z);
     }
-    lx = fpsg_wave_min(lx); ly = fpsg_wave_min(ly); lz = fpsg_wave_min(lz);
+    lx = wave_min_f32(lx); ly = wave_min_f32(ly); lz = wave_min_f32(lz);
     hx = wave_max_f32(hx); hy = wave_max_f32(hy); hz = wave_max_f32(hz);
     if (lane == 0) { red[0 * 16 + wave] = lx; red[1 * 16 + wave] = ly; red[2 * 16 + wave] = lz;
                      red[3 * 16 + wave] = hx; red[4 * 16 + wave] = hy; red[5 * 16 + wave] = hz; }
@@ -113,11 +74,11 @@ __global__ void __launch_bounds__(1024) fps_big_kernel(int n, int m, int bs, int
     for (int q = t; q < NPAD; q += T) {
         unsigned key = 0xffffffffu;  // padding sorts to the end (a real key never reaches it: its index field is < 2^idxbits - 1)
         if (q < n) {
-            const F3g p = fpsg_ld3(xyz, q);
+            const F3 p = ld_point(xyz, q);
             const unsigned cx = (unsigned)fminf(fmaxf((p.x - lx) * scale, 0.f), 1023.f);
             const unsigned cy = (unsigned)fminf(fmaxf((p.y - ly) * scale, 0.f), 1023.f);
             const unsigned cz = (unsigned)fminf(fmaxf((p.z - lz) * scale, 0.f), 1023.f);
-            const unsigned code = fpsg_part1by2(cx) | (fpsg_part1by2(cy) << 1) | (fpsg_part1by2(cz) << 2);
+            const unsigned code = part1by2(cx) | (part1by2(cy) << 1) | (part1by2(cz) << 2);
             key = ((code >> mshift) << idxbits) | (unsigned)q;
         }
         keys[q] = key;
@@ -154,9 +115,9 @@ __global__ void __launch_bounds__(1024) fps_big_kernel(int n, int m, int bs, int
     for (int i = 0; i < P; ++i) {
         const bool ok = G4D_RK(i) != 0xffffu;
         const int k = ok ? fpsg_index16(G4D_RK(i)) : 0;
-        const F3g p = fpsg_ld3(xyz, k);
+        const F3 p = ld_point(xyz, k);
         md[i] = ok ? (temp ? temp[k] : 1e10f) : -2.f;   // -2: below every real min-distance, never a candidate
-        const float a0 = fpsg_wave_min(ok ? p.x : INF), a1 = fpsg_wave_min(ok ? p.y : INF), a2 = fpsg_wave_min(ok ? p.z : INF);
+        const float a0 = wave_min_f32(ok ? p.x : INF), a1 = wave_min_f32(ok ? p.y : INF), a2 = wave_min_f32(ok ? p.z : INF);
         const float a3 = wave_max_f32(ok ? p.x : -INF), a4 = wave_max_f32(ok ? p.y : -INF), a5 = wave_max_f32(ok ? p.z : -INF);
         if (lane == i) { blx = a0; bly = a1; blz = a2; bhx = a3; bhy = a4; bhz = a5; }
         asm volatile("" ::: "memory");   // one slot at a time: left alone the scheduler hoists all P coordinate loads (3 P registers) to the top
@@ -183,7 +144,7 @@ __global__ void __launch_bounds__(1024) fps_big_kernel(int n, int m, int bs, int
         typedef float f32x4 __attribute__((ext_vector_type(4)));
         if (lane < 2) { rec[(wave * 2 + lane) * 4] = 0ull; recf[(wave * 2 + lane) * 8 + 5] = -2.f; }
         if (t == 0) {
-            const F3g p0 = fpsg_ld3(xyz, 0);
+            const F3 p0 = ld_point(xyz, 0);
             nstop[0] = 0xffu; nstop[1] = 0xffu;
             res[0] = p0.x; res[1] = p0.y; res[2] = p0.z; res[3] = INF;
         }
@@ -209,12 +170,12 @@ __global__ void __launch_bounds__(1024) fps_big_kernel(int n, int m, int bs, int
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
                     if (((U >> (8 * g + 4 * h)) & 0xfu) == 0u) continue;   // wave-uniform
-                    F3g p[4];
+                    F3 p[4];
 #pragma unroll
                     for (int s4 = 0; s4 < 4; ++s4) {
                         unsigned r = G4D_RK(8 * g + 4 * h + s4);
                         asm volatile("" : "+v"(r));   // (see the single-pick loop: keeps the row addresses from being hoisted and spilled)
-                        p[s4] = fpsg_ld3(xyz, r == 0xffffu ? 0 : fpsg_index16(r));
+                        p[s4] = ld_point(xyz, r == 0xffffu ? 0 : fpsg_index16(r));
                     }
                     for (int i = 0; i < cnt; ++i) {
                         const unsigned mi = ((unsigned)__builtin_amdgcn_readlane((int)am, i) >> (8 * g + 4 * h)) & 0xfu;
@@ -225,7 +186,7 @@ __global__ void __launch_bounds__(1024) fps_big_kernel(int n, int m, int bs, int
                         for (int s4 = 0; s4 < 4; ++s4)
                             if ((mi >> s4) & 1u) {
                                 const float dx = p[s4].x - ax, dy = p[s4].y - ay, dz = p[s4].z - az;
-                                md[8 * g + 4 * h + s4] = fpsg_min(dist2<FM>(dx, dy, dz), md[8 * g + 4 * h + s4]);
+                                md[8 * g + 4 * h + s4] = bare_min_f32(dist2<FM>(dx, dy, dz), md[8 * g + 4 * h + s4]);
                             }
                     }
                 }
@@ -237,13 +198,13 @@ __global__ void __launch_bounds__(1024) fps_big_kernel(int n, int m, int bs, int
                 // the lane's best and second-best slot (value, then smallest rank)
                 float b1 = md[0];
 #pragma unroll
-                for (int i = 1; i < P; ++i) b1 = fpsg_max(b1, md[i]);
+                for (int i = 1; i < P; ++i) b1 = bare_max_f32(b1, md[i]);
                 unsigned r1 = 0xffffu;
 #pragma unroll
                 for (int i = 0; i < P; ++i) r1 = min(r1, md[i] == b1 ? G4D_RK(i) : 0xffffu);
                 float b2 = -2.f;
 #pragma unroll
-                for (int i = 0; i < P; ++i) b2 = fpsg_max(b2, G4D_RK(i) == r1 ? -2.f : md[i]);   // ranks of real points are unique: drops exactly the best slot
+                for (int i = 0; i < P; ++i) b2 = bare_max_f32(b2, G4D_RK(i) == r1 ? -2.f : md[i]);   // ranks of real points are unique: drops exactly the best slot
                 unsigned r2 = 0xffffu;
 #pragma unroll
                 for (int i = 0; i < P; ++i) r2 = min(r2, (md[i] == b2 && G4D_RK(i) != r1) ? G4D_RK(i) : 0xffffu);
@@ -264,7 +225,7 @@ __global__ void __launch_bounds__(1024) fps_big_kernel(int n, int m, int bs, int
                 if (lane < 2) {
                     const float cvv = lane == 0 ? c1v : c2v;
                     const unsigned c16 = lane == 0 ? c1r : c2r;
-                    const unsigned r32 = ((c16 >> 5) << 16) | (c16 & 31u);   // the 32-bit rank of fpsg_rank
+                    const unsigned r32 = ((c16 >> 5) << 16) | (c16 & 31u);   // the 32-bit rank of fps_rank
                     rec[(wave * 2 + lane) * 4] = (cvv < 0.f || c16 == 0xffffu) ? 0ull : (((unsigned long long)__float_as_uint(cvv) << 32) | (unsigned)(~r32));
                     recf[(wave * 2 + lane) * 8 + 5] = v3w;
                 }
@@ -279,7 +240,7 @@ __global__ void __launch_bounds__(1024) fps_big_kernel(int n, int m, int bs, int
                 int ij = fpsg_index(~(unsigned)kj, log2bs), im = fpsg_index(~(unsigned)km, log2bs);
                 ij = (kj != 0ull && (unsigned)ij < (unsigned)n) ? ij : 0;   // (an empty slot reads point 0: never used)
                 im = (km != 0ull && (unsigned)im < (unsigned)n) ? im : 0;
-                const F3g pj = fpsg_ld3(xyz, ij), pm = fpsg_ld3(xyz, im);
+                const F3 pj = ld_point(xyz, ij), pm = ld_point(xyz, im);
                 const float mv = __uint_as_float((unsigned)(km >> 32));
                 const bool gt = kj > km;
                 const bool aff = gt && !(dist2<FM>(pm.x - pj.x, pm.y - pj.y, pm.z - pj.z) >= mv);
@@ -315,7 +276,7 @@ __global__ void __launch_bounds__(1024) fps_big_kernel(int n, int m, int bs, int
         if (temp && ns > 1) sweep(ns - 1, INF);
     } else {
     float x1, y1, z1;
-    { const F3g p0 = fpsg_ld3(xyz, 0); x1 = p0.x; y1 = p0.y; z1 = p0.z; }
+    { const F3 p0 = ld_point(xyz, 0); x1 = p0.x; y1 = p0.y; z1 = p0.z; }
     float gval = INF;          // the last winner's value: no min-distance exceeds it
     float gb[G];               // cached (value, rank) candidate of each group of 8 slots
     unsigned gr[G];            // (16-bit ranks)
@@ -341,18 +302,18 @@ __global__ void __launch_bounds__(1024) fps_big_kernel(int n, int m, int bs, int
                 for (int h = 0; h < 2; ++h) {
                     const unsigned ah = (ag >> (4 * h)) & 0xfu;
                     if (ah == 0u) continue;   // wave-uniform
-                    F3g p[4];
+                    F3 p[4];
 #pragma unroll
                     for (int s = 0; s < 4; ++s) {
                         unsigned r = G4D_RK(8 * g + 4 * h + s);
                         asm volatile("" : "+v"(r));   // the ranks never change: left visible, the row addresses (2 registers per slot) are hoisted out of the round loop and spilled
-                        p[s] = fpsg_ld3(xyz, r == 0xffffu ? 0 : fpsg_index16(r));
+                        p[s] = ld_point(xyz, r == 0xffffu ? 0 : fpsg_index16(r));
                     }
 #pragma unroll
                     for (int s = 0; s < 4; ++s) {
                         if ((ah >> s) & 1u) {
                             const float dx = p[s].x - x1, dy = p[s].y - y1, dz = p[s].z - z1;
-                            md[8 * g + 4 * h + s] = fpsg_min(dist2<FM>(dx, dy, dz), md[8 * g + 4 * h + s]);
+                            md[8 * g + 4 * h + s] = bare_min_f32(dist2<FM>(dx, dy, dz), md[8 * g + 4 * h + s]);
                         }
                     }
                 }
@@ -363,7 +324,7 @@ __global__ void __launch_bounds__(1024) fps_big_kernel(int n, int m, int bs, int
 #pragma unroll
                 for (int w = 8; w > 1; w >>= 1)
 #pragma unroll
-                    for (int s = 0; s < w / 2; ++s) tv[s] = fpsg_max(tv[s], tv[s + w / 2]);
+                    for (int s = 0; s < w / 2; ++s) tv[s] = bare_max_f32(tv[s], tv[s + w / 2]);
                 unsigned tr[8];
 #pragma unroll
                 for (int s = 0; s < 8; ++s) tr[s] = (md[8 * g + s] == tv[0]) ? G4D_RK(8 * g + s) : 0xffffu;
@@ -377,7 +338,7 @@ __global__ void __launch_bounds__(1024) fps_big_kernel(int n, int m, int bs, int
             // 3b. lane candidate = best group candidate; then the wave's
             float b = gb[0];
 #pragma unroll
-            for (int g = 1; g < G; ++g) b = fpsg_max(b, gb[g]);
+            for (int g = 1; g < G; ++g) b = bare_max_f32(b, gb[g]);
             unsigned r = 0xffffu;
 #pragma unroll
             for (int g = 0; g < G; ++g) r = min(r, gb[g] == b ? gr[g] : 0xffffu);
@@ -386,7 +347,7 @@ __global__ void __launch_bounds__(1024) fps_big_kernel(int n, int m, int bs, int
             unsigned c16;
             if (__builtin_popcountll(hit) == 1) c16 = (unsigned)__builtin_amdgcn_readlane((int)r, __builtin_ctzll(hit));
             else c16 = wave_min_u32(b == cval ? r : 0xffffu);
-            crank = c16 == 0xffffu ? 0xffffffffu : (((c16 >> 5) << 16) | (c16 & 31u));   // the exchange key carries the 32-bit rank of fpsg_rank
+            crank = c16 == 0xffffu ? 0xffffffffu : (((c16 >> 5) << 16) | (c16 & 31u));   // the exchange key carries the 32-bit rank of fps_rank
         }
         // 4. workgroup arg-max: one LDS atomic max per wave on a rotating slot, one barrier, one read
         if (lane == 0)
@@ -399,7 +360,7 @@ __global__ void __launch_bounds__(1024) fps_big_kernel(int n, int m, int bs, int
         gval = __uint_as_float(bhi);
         int old = fpsg_index(rank, log2bs);
         old = (unsigned)old < (unsigned)n ? old : 0;     // (no candidate anywhere -- all-NaN clouds: the reference picks index 0 too)
-        const F3g pw = fpsg_ld3(xyz, old);               // the winner's coordinates: one broadcast load (L2)
+        const F3 pw = ld_point(xyz, old);               // the winner's coordinates: one broadcast load (L2)
         x1 = pw.x; y1 = pw.y; z1 = pw.z;
         if (t == 0) spick[j] = old;
     }
@@ -408,7 +369,7 @@ __global__ void __launch_bounds__(1024) fps_big_kernel(int n, int m, int bs, int
     for (int j = t; j < m; j += T) {
         const int k = spick[j];
         idx[j] = k;
-        if (nx) { const F3g p = fpsg_ld3(xyz, k); nx[j * 3 + 0] = p.x; nx[j * 3 + 1] = p.y; nx[j * 3 + 2] = p.z; }
+        if (nx) { const F3 p = ld_point(xyz, k); nx[j * 3 + 0] = p.x; nx[j * 3 + 1] = p.y; nx[j * 3 + 2] = p.z; }
     }
     if (temp) {
 #pragma unroll
@@ -426,7 +387,7 @@ static int launch_big(int b, int n, int m, int bs, int log2bs, const float *xyz,
     static unsigned long long attr[6] = {0, 0, 0, 0, 0, 0};
     const int mode = distance_contraction();
     const void *k = nullptr;
-    static const int multi = getenv("G4D_FPS_BIG_MULTI") ? atoi(getenv("G4D_FPS_BIG_MULTI")) : 1;   // 0: one pick per round (the round-3 loop)
+    static const int multi = env_int("G4D_FPS_BIG_MULTI", 1);   // 0: one pick per round (the round-3 loop)
     G4D_WITH_FM(mode, k = multi ? reinterpret_cast<const void *>(fps_big_kernel<P, FM, true>) : reinterpret_cast<const void *>(fps_big_kernel<P, FM, false>))
     if (const int rc = ensure_dynamic_lds(k, 160 * 1024 - 1024, attr[(mode == 0 ? 0 : (mode == 1 ? 1 : 2)) + (multi ? 3 : 0)], "g4d_fps_f32(large)")) return rc;
     if (multi) { G4D_WITH_FM(mode, hipLaunchKernelGGL((fps_big_kernel<P, FM, true>), dim3(b), dim3(1024), lds, s, n, m, bs, log2bs, idxbits, xyz, temp, idx, nx)) }
@@ -436,7 +397,7 @@ static int launch_big(int b, int n, int m, int bs, int log2bs, const float *xyz,
 
 // Called by fps_impl (fps.hip) for 8192 < n <= 32768 when the register-resident kernel does not take the shape.  -1: not covered.
 int fps_big_dispatch(int b, int n, int m, int bs, int log2bs, const float *xyz, float *temp, int *idx, float *nx, hipStream_t s) {
-    static const int on = getenv("G4D_FPS_BIG") ? atoi(getenv("G4D_FPS_BIG")) : 1;
+    static const int on = env_int("G4D_FPS_BIG", 1);
     if (!on || n <= 8192 || n > 32768 || m > n || bs != 1024 || log2bs != 10) return -1;   // (bs = 1024 for every n >= 1024: the 16-bit rank packing relies on it)
     if (n <= 16384) return launch_big<16>(b, n, m, bs, log2bs, xyz, temp, idx, nx, s);
     return launch_big<32>(b, n, m, bs, log2bs, xyz, temp, idx, nx, s);

@@ -39,74 +39,6 @@ constexpr int kFpsHdr = 2048;   // LDS header in front of the sort arrays / SoA 
 constexpr int kFpsRecX = 256, kFpsRecV3 = kFpsRecX + 3 * 128;   // multi-pick rounds: the candidates' x | y | z arrays and the waves' third-best values (keys at 0)
 constexpr int kFpsCellBits = 12, kFpsCells = 1 << kFpsCellBits;   // coarse Morton cells of the counting sort (16 x 16 x 16 over the cloud's box)
 
-// --- pieces shared with fps.hip (kept local: both files are self-contained translation units)
-__device__ __forceinline__ unsigned fpsb_rank(int k, int bs, int log2bs) {
-    const unsigned c = (unsigned)k & (unsigned)(bs - 1);
-    const unsigned q = (unsigned)k >> log2bs;
-    const unsigned br = log2bs ? (__builtin_bitreverse32(c) >> (32 - log2bs)) : 0u;
-    return (br << 16) | q;
-}
-
-__device__ __forceinline__ float fpsb_min(float a, float b) {
-    float r;
-    asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-
-template <int W>
-__device__ __forceinline__ unsigned long long fpsb_row_max_u64(unsigned long long key) {
-#define G4D_STEP(CTRL)                                                                                       \
-    {                                                                                                        \
-        const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)key, CTRL, 0xf, 0xf, true);        \
-        const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(key >> 32), CTRL, 0xf, 0xf, true); \
-        const unsigned long long o = ((unsigned long long)hi << 32) | lo;                                    \
-        key = o > key ? o : key;                                                                             \
-    }
-    G4D_STEP(0x111)
-    G4D_STEP(0x112)
-    if constexpr (W >= 8) G4D_STEP(0x114)
-    if constexpr (W >= 16) G4D_STEP(0x118)
-#undef G4D_STEP
-    return key;
-}
-
-__device__ __forceinline__ float fmax_raw(float a, float b) {  // bare v_max_f32: no canonicalising pre-pass (inputs are never NaN)
-    float r;
-    asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-
-__device__ __forceinline__ float wave_min_f32(float v) {
-    int out;
-    asm volatile(
-        "s_nop 1\n\t"
-        "v_min_f32_dpp %0, %0, %0 row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_min_f32_dpp %0, %0, %0 row_shr:2 row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_min_f32_dpp %0, %0, %0 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_min_f32_dpp %0, %0, %0 row_shr:8 row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_min_f32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_min_f32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_readlane_b32 %1, %0, 63\n\t"
-        "s_nop 3"
-        : "+v"(v), "=s"(out));
-    return __int_as_float(out);
-}
-
-__device__ __forceinline__ unsigned part1by2(unsigned v) {  // spread the low 10 bits: b9..b0 -> every third bit
-    v &= 0x3ffu;
-    v = (v | (v << 16)) & 0x030000ffu;
-    v = (v | (v << 8)) & 0x0300f00fu;
-    v = (v | (v << 4)) & 0x030c30c3u;
-    v = (v | (v << 2)) & 0x09249249u;
-    return v;
-}
-
 // W waves, P buckets (slots) per wave; handles N <= 64*W*P points.  LDS: header + max(4*(4096 + Npad) sort arrays, 12*N SoA) + the pick list.
 // KMAX > 1: the multi-pick round loop (below); KMAX = 1: one sample per round.
 // SOA: the LDS copy of the cloud (96 KB at n = 8192) that the winner's coordinates are read from.  SOA = false (multi-pick rounds only,
@@ -250,7 +182,7 @@ __device__ __forceinline__ void fps_bucket_body(int n, int m, int bs, int log2bs
 #pragma unroll
     for (int i = 0; i < P; ++i) {
         const bool ok = pk[i] >= 0;
-        rk[i] = ok ? ((fpsb_rank(pk[i], bs, log2bs) << SB) | (SOA ? 0u : (unsigned)i)) : 0xffffffffu;
+        rk[i] = ok ? ((fps_rank(pk[i], bs, log2bs) << SB) | (SOA ? 0u : (unsigned)i)) : 0xffffffffu;
         const float a0 = wave_min_f32(ok ? px(i) : INF), a1 = wave_min_f32(ok ? py(i) : INF), a2 = wave_min_f32(ok ? pz(i) : INF);
         const float a3 = wave_max_f32(ok ? px(i) : -INF), a4 = wave_max_f32(ok ? py(i) : -INF), a5 = wave_max_f32(ok ? pz(i) : -INF);
         if ((lane & (P - 1)) == i) { blx = a0; bly = a1; blz = a2; bhx = a3; bhy = a4; bhz = a5; }   // lane l holds the box of bucket l % P
@@ -366,7 +298,7 @@ __device__ __forceinline__ void fps_bucket_body(int n, int m, int bs, int log2bs
                     for (int q = 0; q < P; ++q) {
                         if ((mi >> q) & 1u) {
                             const float dx = px(q) - ax, dy = py(q) - ay, dz = pz(q) - az;
-                            md(q) = fpsb_min(dist2<FM>(dx, dy, dz), md(q));
+                            md(q) = bare_min_f32(dist2<FM>(dx, dy, dz), md(q));
                         }
                     }
                 }
@@ -385,7 +317,7 @@ __device__ __forceinline__ void fps_bucket_body(int n, int m, int bs, int log2bs
 #pragma unroll
                 for (int w = P; w > 1; w >>= 1)
 #pragma unroll
-                    for (int i = 0; i < w / 2; ++i) tv[i] = fmax_raw(tv[i], tv[i + w / 2]);
+                    for (int i = 0; i < w / 2; ++i) tv[i] = bare_max_f32(tv[i], tv[i + w / 2]);
                 const float b1 = tv[0];
                 unsigned tr[P];
 #pragma unroll
@@ -400,7 +332,7 @@ __device__ __forceinline__ void fps_bucket_body(int n, int m, int bs, int log2bs
 #pragma unroll
                 for (int w = P; w > 1; w >>= 1)
 #pragma unroll
-                    for (int i = 0; i < w / 2; ++i) tv[i] = fmax_raw(tv[i], tv[i + w / 2]);
+                    for (int i = 0; i < w / 2; ++i) tv[i] = bare_max_f32(tv[i], tv[i + w / 2]);
                 const float b2 = tv[0];
 #pragma unroll
                 for (int i = 0; i < P; ++i) tr[i] = (md(i) == b2 && rk[i] != r1) ? rk[i] : 0xffffffffu;
@@ -563,7 +495,7 @@ __device__ __forceinline__ void fps_bucket_body(int n, int m, int bs, int log2bs
                     const float az = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(zs), i * P));
 #pragma unroll
                     for (int q = 0; q < P; ++q)
-                        if ((mi >> q) & 1u) md(q) = fpsb_min(dist2<FM>(px(q) - ax, py(q) - ay, pz(q) - az), md(q));
+                        if ((mi >> q) & 1u) md(q) = bare_min_f32(dist2<FM>(px(q) - ax, py(q) - ay, pz(q) - az), md(q));
                 }
             }
         }
@@ -603,7 +535,7 @@ __device__ __forceinline__ void fps_bucket_body(int n, int m, int bs, int log2bs
                 for (int i = 0; i < P; ++i) {
                     if ((active >> i) & 1u) {
                         const float dx = px(i) - x1, dy = py(i) - y1, dz = pz(i) - z1;
-                        md(i) = fpsb_min(dist2<FM>(dx, dy, dz), md(i));
+                        md(i) = bare_min_f32(dist2<FM>(dx, dy, dz), md(i));
                     }
                 }
                 // 3. lane candidate: max value over its P points, smallest rank among the points holding it; then the wave's
@@ -614,7 +546,7 @@ __device__ __forceinline__ void fps_bucket_body(int n, int m, int bs, int log2bs
 #pragma unroll
                 for (int w = P; w > 1; w >>= 1)
 #pragma unroll
-                    for (int i = 0; i < w / 2; ++i) tv[i] = fmax_raw(tv[i], tv[i + w / 2]);
+                    for (int i = 0; i < w / 2; ++i) tv[i] = bare_max_f32(tv[i], tv[i + w / 2]);
                 const float b = tv[0];
                 unsigned tr[P];
 #pragma unroll
@@ -708,7 +640,7 @@ fps_bucket_reg_kernel(int n, int m, int bs, int log2bs, int deal, int pick_off, 
 // on a uniform 8192 -> 1024 cloud 236 -> 166 rounds (numpy emulation: stops after a wave's second key 123 -> hidden-key stops 53, cap 23 -> 7).
 constexpr int kFpsPicks = 16;
 static int fps_multi() {
-    static const int k = getenv("G4D_FPS_MULTI") ? atoi(getenv("G4D_FPS_MULTI")) : 8;
+    static const int k = env_int("G4D_FPS_MULTI", 8);
     return k > 1 ? 8 : 1;
 }
 // Which multi-pick form a launch of b clouds takes.  The LDS-copy form (rounds 3-4: 74 VGPRs, 104 KB) has the shorter round (0.61 us per pick
@@ -718,11 +650,11 @@ static int fps_multi() {
 // fp32, 94.4k -> 96.8k bf16 (profiles/r05_overlap_pairs_240clouds.txt: next to fp_init 0.98 -> 0.80 of the sum, next to the tiled GEMMs
 // 0.97 -> 0.86-0.91).  G4D_FPS_SOA=1 / 0 forces one form.
 static bool fps_soa(int b) {
-    static const int k = getenv("G4D_FPS_SOA") ? atoi(getenv("G4D_FPS_SOA")) : -1;
+    static const int k = env_int("G4D_FPS_SOA", -1);
     return k < 0 ? b < 32 : k != 0;
 }
 static int fps_kcap() {   // tuning hook: at most this many samples per round
-    static const int k = getenv("G4D_FPS_KCAP") ? atoi(getenv("G4D_FPS_KCAP")) : kFpsPicks;
+    static const int k = env_int("G4D_FPS_KCAP", kFpsPicks);
     return k < 1 ? 1 : (k > 64 ? 64 : k);
 }
 
@@ -765,7 +697,7 @@ static int launch_bucket_fm(int b, int n, int m, int bs, int log2bs, const float
     static unsigned long long attr_done[3] = {0, 0, 0};  // one bit per device
     if (const int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(kern), 160 * 1024 - 1024, attr_done[multi ? (soa ? 1 : 2) : 0], "g4d_fps_f32(bucketed)")) return rc;
     // measured at N = 8192, M = 1024, B = 8 (scripts/time_fps.py): deal 1 / 2 / 4 / 8 -> 0.812 / 0.783 / 0.757 / 0.748 us per round
-    static const int deal_env = getenv("G4D_FPS_DEAL") ? atoi(getenv("G4D_FPS_DEAL")) : 0;  // tuning hook: 1 | 2 | 4 | ... | P; 0 = P
+    static const int deal_env = env_int("G4D_FPS_DEAL", 0);  // tuning hook: 1 | 2 | 4 | ... | P; 0 = P
     const int deal = (deal_env >= 1 && deal_env <= P && P % deal_env == 0) ? deal_env : P;
     hipLaunchKernelGGL(kern, dim3(b), dim3(64 * W), lds, s, n, m, bs, log2bs, deal | (fps_kcap() << 8), (int)pick_off, xyz, temp, idx, nx);
     return check_launch("g4d_fps_f32(bucketed)");
@@ -807,7 +739,7 @@ int fps_bucket_grid_launch(int b, int n, int m, int bs, int log2bs, const float 
 
 // Called by g4d_fps_f32 (fps.hip) for 2048 < n <= 8192.  Returns -1 when the shape is not covered.
 int fps_bucket_dispatch(int b, int n, int m, int bs, int log2bs, const float *xyz, float *temp, int *idx, float *nx, hipStream_t s) {
-    static const int cfg = getenv("G4D_FPS_BUCKET_W") ? atoi(getenv("G4D_FPS_BUCKET_W")) : 16;  // tuning hook
+    static const int cfg = env_int("G4D_FPS_BUCKET_W", 16);  // tuning hook
     if (n > 4096 && n <= 8192) {
         if (cfg == 8) return launch_bucket<8, 16>(b, n, m, bs, log2bs, xyz, temp, idx, nx, s);
         if (cfg == 4) return launch_bucket<4, 32>(b, n, m, bs, log2bs, xyz, temp, idx, nx, s);

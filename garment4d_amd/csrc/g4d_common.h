@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 
 #include "../../include/g4d.h"
 
@@ -123,6 +124,30 @@ inline int ensure_dynamic_lds(const void *kernel, int bytes, unsigned long long 
     return G4D_OK;
 }
 
+// Grid of a persistent kernel: the workgroups of `threads` threads and `dynamic_lds` bytes that are resident on the whole device at once
+// (one per CU when the occupancy query fails, 256 CUs when the device does not say).  Callers cache the result.
+inline int device_cus() {
+    int dev = 0;
+    hipDeviceProp_t prop;
+    return (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
+}
+template <class Kernel>
+inline int resident_workgroups(Kernel kernel, int threads, int dynamic_lds) {
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, dynamic_lds) != hipSuccess || per_cu < 1) per_cu = 1;
+    return per_cu * device_cus();
+}
+
+// A/B switches and tuning values read from the environment: `static const int x = env_int("G4D_X", dflt);` reads it once per process.
+inline int env_int(const char *name, int dflt) {
+    const char *v = getenv(name);
+    return v ? atoi(v) : dflt;
+}
+inline long long env_ll(const char *name, long long dflt) {
+    const char *v = getenv(name);
+    return v ? atoll(v) : dflt;
+}
+
 // ---- wave-level primitives (DPP, no LDS) ------------------------------------------------------
 // dpp_ctrl encodings: row_shr:n = 0x110+n, row_bcast:15 = 0x142, row_bcast:31 = 0x143.
 template <int CTRL, int ROW_MASK>
@@ -160,6 +185,99 @@ __device__ __forceinline__ float wave_max_f32(float v) {
         "s_nop 3"
         : "+v"(v), "=s"(out));
     return __int_as_float(out);
+}
+
+// min over the 64 lanes: wave_max_f32's chain with v_min_f32_dpp -- no NaNs expected in v, result wave-uniform (SGPR).
+__device__ __forceinline__ float wave_min_f32(float v) {
+    int out;
+    asm volatile(
+        "s_nop 1\n\t"
+        "v_min_f32_dpp %0, %0, %0 row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
+        "s_nop 1\n\t"
+        "v_min_f32_dpp %0, %0, %0 row_shr:2 row_mask:0xf bank_mask:0xf\n\t"
+        "s_nop 1\n\t"
+        "v_min_f32_dpp %0, %0, %0 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
+        "s_nop 1\n\t"
+        "v_min_f32_dpp %0, %0, %0 row_shr:8 row_mask:0xf bank_mask:0xf\n\t"
+        "s_nop 1\n\t"
+        "v_min_f32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
+        "s_nop 1\n\t"
+        "v_min_f32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf\n\t"
+        "s_nop 1\n\t"
+        "v_readlane_b32 %1, %0, 63\n\t"
+        "s_nop 3"
+        : "+v"(v), "=s"(out));
+    return __int_as_float(out);
+}
+
+// min / max over the 64 lanes as an xor butterfly of fminf / fmaxf: a NaN is dropped, the result ends up in EVERY lane (VGPR).
+__device__ __forceinline__ float wave_min_all(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o));
+    return v;
+}
+__device__ __forceinline__ float wave_max_all(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+    return v;
+}
+
+// The bare instructions: fminf() / fmaxf() make hipcc canonicalise a loop-carried operand first (an extra v_max x, x per point); these have the
+// semantics wanted where no operand is a signalling NaN (IEEE mode: a NaN operand yields the other operand).
+__device__ __forceinline__ float bare_min_f32(float a, float b) {
+    float r;
+    asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+__device__ __forceinline__ float bare_max_f32(float a, float b) {
+    float r;
+    asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+
+// max of W (4/8/16) 64-bit keys held by lanes 0..W-1 of each 16-lane row (Hillis-Steele with row_shr; lanes
+// without a source read 0, which never wins).  Result valid in lane W-1.
+template <int W>
+__device__ __forceinline__ unsigned long long row_max_u64(unsigned long long key) {
+#define G4D_STEP(CTRL)                                                                                       \
+    {                                                                                                        \
+        const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)key, CTRL, 0xf, 0xf, true);        \
+        const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(key >> 32), CTRL, 0xf, 0xf, true); \
+        const unsigned long long o = ((unsigned long long)hi << 32) | lo;                                    \
+        key = o > key ? o : key;                                                                             \
+    }
+    G4D_STEP(0x111)
+    G4D_STEP(0x112)
+    if constexpr (W >= 8) G4D_STEP(0x114)
+    if constexpr (W >= 16) G4D_STEP(0x118)
+#undef G4D_STEP
+    return key;
+}
+
+// FPS tie rank of point k, bs = min(1024, 2^floor(log2 n)): (bitrev(k mod bs) << 16) | k / bs -- smaller wins among equal distances, which is
+// the order the reference's strided scan + shared-memory tree resolves ties in (fps.hip)
+__device__ __forceinline__ unsigned fps_rank(int k, int bs, int log2bs) {
+    const unsigned c = (unsigned)k & (unsigned)(bs - 1);
+    const unsigned q = (unsigned)k >> log2bs;
+    const unsigned br = log2bs ? (__builtin_bitreverse32(c) >> (32 - log2bs)) : 0u;
+    return (br << 16) | q;
+}
+
+__device__ __forceinline__ unsigned part1by2(unsigned v) {  // Morton codes: spread the low 10 bits, b9..b0 -> every third bit
+    v &= 0x3ffu;
+    v = (v | (v << 16)) & 0x030000ffu;
+    v = (v | (v << 8)) & 0x0300f00fu;
+    v = (v | (v << 4)) & 0x030c30c3u;
+    v = (v | (v << 2)) & 0x09249249u;
+    return v;
+}
+
+// A point as it lies in an (n, 3) array: 12 bytes, 4-byte aligned -- one 12-byte load, one cache-line lookup per row instead of three.
+struct __attribute__((packed, aligned(4))) F3 { float x, y, z; };
+__device__ __forceinline__ F3 ld_point(const float *xyz, int k) { return *reinterpret_cast<const F3 *>(xyz + (size_t)k * 3); }   // point k
+// ... at a 32-bit ELEMENT offset from a uniform base (`global_load v, v_off, s[base]`: one VALU op per address; the tensor is < 4 GB)
+__device__ __forceinline__ F3 ld_f3(const float *base, unsigned elem) {
+    return *reinterpret_cast<const F3 *>(reinterpret_cast<const char *>(base) + (elem << 2));
 }
 
 __device__ __forceinline__ unsigned wave_min_u32(unsigned v) {

@@ -93,7 +93,7 @@ static int gemm_narrow_launch(const LinearArgs &a, hipStream_t s) {
 
 // Used by launch_linear (mlp.hip) ahead of the wider GEMM forms: true when the launch was taken.
 bool gemm_narrow_try(const LinearArgs &a, hipStream_t s, int *rc) {
-    static const int enabled = [] { const char *e = getenv("G4D_GEMM_NARROW"); return e ? atoi(e) : 1; }();   // A/B switch
+    static const int enabled = env_int("G4D_GEMM_NARROW", 1);   // A/B switch
     if (!enabled || a.pool != 0 || a.tab || a.rows < 32768 || a.K != a.Kpad || (a.ldx & 3) || (a.ldo & 3) || (a.col0 & 3) ||
         (reinterpret_cast<size_t>(a.X) & 15) || (reinterpret_cast<size_t>(a.out) & 15))
         return false;

@@ -144,8 +144,8 @@ __global__ void __launch_bounds__(GT, 2) gemm_stream_kernel(const LinearArgs a, 
 
 // Used by launch_linear (mlp.hip) for DIRECT launches without pooling: true when the launch was taken.
 bool gemm_stream_try(const LinearArgs &a, hipStream_t s, int *rc) {
-    static const int enabled = [] { const char *e = getenv("G4D_GEMM_STREAM"); return e ? atoi(e) : 1; }();
-    static const long long min_rows = [] { const char *e = getenv("G4D_GEMM_STREAM_MIN_ROWS"); return e ? atoll(e) : 65536ll; }();
+    static const int enabled = env_int("G4D_GEMM_STREAM", 1);
+    static const long long min_rows = env_ll("G4D_GEMM_STREAM_MIN_ROWS", 65536ll);
     const int cpad = (a.Cout + 63) / 64 * 64;   // the packed weight / scale / shift are padded to 64 channels
     if (!enabled || a.pool != 0 || a.rows < min_rows || cpad % GN != 0 || a.Kpad > 128 || a.tab) return false;   // (tab: the interpolate-add epilogue lives in mlp.hip / gemm_tile.hip)
     static unsigned long long attr = 0;
@@ -162,7 +162,7 @@ bool gemm_stream_try(const LinearArgs &a, hipStream_t s, int *rc) {
     int gx = 2 * cus / ncol > 0 ? 2 * cus / ncol : 1;   // two persistent workgroups per CU in total (70 KB of LDS each)
     if (gx > ntiles) gx = ntiles;
     const unsigned long long ob = (unsigned long long)a.rows * a.ldo * sizeof(float);
-    static const int use_buf = [] { const char *e = getenv("G4D_GEMM_BUFFER_STORES"); return e ? atoi(e) : 1; }();
+    static const int use_buf = env_int("G4D_GEMM_BUFFER_STORES", 1);
     if (use_buf && ob < 0x7fffffffull) hipLaunchKernelGGL(gemm_stream_kernel<true>, dim3((unsigned)gx, (unsigned)ncol), dim3(GT), lds, s, a, ntiles, (unsigned)ob);
     else hipLaunchKernelGGL(gemm_stream_kernel<false>, dim3((unsigned)gx, (unsigned)ncol), dim3(GT), lds, s, a, ntiles, 0u);
     *rc = check_launch("g4d_linear_f32(stream)");

@@ -275,10 +275,10 @@ bool gemm_tile_try(const LinearArgs &a, hipStream_t s, int *rc) {
     const int min_cout = (int)tuning("gemm_tile_min_cout", 128), min_kpad = (int)tuning("gemm_tile_min_kpad", 128);   // (A/B switches; 256 / 256 until the epilogue stored 16 bytes per lane)
     if (!enabled || a.pool != 0 || a.rows < min_rows || a.Kpad < (a.tab ? 128 : min_kpad) || a.Cout < min_cout || a.Cout % TN != 0 || (a.K & 3) || (a.ldx & 3) || (reinterpret_cast<size_t>(a.X) & 15)) return false;
     if (a.tab && ((a.tab_ld & 3) || (reinterpret_cast<size_t>(a.tab) & 15) || a.n <= 0 || (a.rows / a.n + 1) * (long long)a.m * a.tab_ld >= (1ll << 32))) return false;
-    static const int lds_extra = getenv("G4D_GEMM_TILE_LDS_EXTRA") ? atoi(getenv("G4D_GEMM_TILE_LDS_EXTRA")) : 0;   // experiment: > 0 forces one workgroup per CU
+    static const int lds_extra = env_int("G4D_GEMM_TILE_LDS_EXTRA", 0);   // experiment: > 0 forces one workgroup per CU
     const int lds = 2 * (TM + TN) * TLD * (int)sizeof(float) + lds_extra;   // 81920 bytes: two workgroups per CU fill its 160 KB exactly
     typedef void (*Kern)(const LinearArgs, int, int, int, int);
-    static const int d2 = getenv("G4D_GEMM_TILE_D2") ? atoi(getenv("G4D_GEMM_TILE_D2")) : 0;   // A/B switch: prefetch two chunks ahead (measured: no gain, 32 more registers -- off; never for the interp-add form)
+    static const int d2 = env_int("G4D_GEMM_TILE_D2", 0);   // A/B switch: prefetch two chunks ahead (measured: no gain, 32 more registers -- off; never for the interp-add form)
     static const Kern kerns[8] = {gemm_tile_kernel<false, false, 2, false>, gemm_tile_kernel<false, true, 2, false>, gemm_tile_kernel<true, false, 2, false>, gemm_tile_kernel<true, true, 2, false>,
                                   gemm_tile_kernel<false, false, 2, true>, gemm_tile_kernel<false, true, 2, false>, gemm_tile_kernel<true, false, 2, true>, gemm_tile_kernel<true, true, 2, false>};
     const int wn = 2;
@@ -291,13 +291,8 @@ bool gemm_tile_try(const LinearArgs &a, hipStream_t s, int *rc) {
     const long long blocks = (long long)((nrow + 7) / 8) * 8 * ncol;   // XCD-major numbering: row blocks rounded up to a multiple of 8
     if (blocks >= (1ll << 31)) return false;
     // persistent: two workgroups per CU by LDS; the grid a multiple of 8 so that a workgroup's blocks stay on one XCD's row blocks
-    static const int resident = [] {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        const int cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-        return (2 * cus) / 8 * 8;
-    }();
-    static const int persist = getenv("G4D_GEMM_TILE_PERSIST") ? atoi(getenv("G4D_GEMM_TILE_PERSIST")) : 1;   // A/B switch
+    static const int resident = (2 * device_cus()) / 8 * 8;
+    static const int persist = env_int("G4D_GEMM_TILE_PERSIST", 1);   // A/B switch
     const long long grid = persist && blocks > resident ? resident : blocks;
     hipLaunchKernelGGL(kerns[which], dim3((unsigned)grid), dim3(wn == 4 ? 512 : 256), lds, s, a, nrow, ncol, cpad, (int)blocks);
     *rc = check_launch("g4d_linear_f32(tile)");

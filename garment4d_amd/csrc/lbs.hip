@@ -835,7 +835,7 @@ extern "C" int g4d_lbs_one_f32(int b, int v, int j, int nb, int pose2rot, const 
     if (rc) return rc;
     // frame groups per vertex tile: all of them side by side while that still leaves under ~3 workgroups per CU, else a share each
     const int vt = (v + 63) / 64, ngroups = (b + kFB - 1) / kFB;
-    static const int gy_env = getenv("G4D_LBS_ONE_GROUPS") ? atoi(getenv("G4D_LBS_ONE_GROUPS")) : 0;   // tuning hook
+    static const int gy_env = env_int("G4D_LBS_ONE_GROUPS", 0);   // tuning hook
     int gy = ngroups;
     if (gy_env > 0) gy = gy_env < ngroups ? gy_env : ngroups;
     else if ((long long)vt * ngroups > 768) { gy = (768 + vt - 1) / vt; if (gy > ngroups) gy = ngroups; if (gy < 1) gy = 1; }

@@ -627,7 +627,7 @@ extern "C" int g4d_launch_group_end(g4d_stream_t stream, int *launches) {
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int n = g_group.n;
     g_group.n = 0;
-    static const int merge = getenv("G4D_LAUNCH_GROUPS") ? atoi(getenv("G4D_LAUNCH_GROUPS")) : 1;   // A/B switch: 0 = one launch per recorded stack
+    static const int merge = env_int("G4D_LAUNCH_GROUPS", 1);   // A/B switch: 0 = one launch per recorded stack
     if (launches) *launches = n;
     if (n == 2 && merge) {
         const ChainRole &r0 = g_group.role[0], &r1 = g_group.role[1];
@@ -656,7 +656,7 @@ int g4d::mlp_chain_f32_run(const StackCall &c, hipStream_t st) {
     if (const int rc = stack_call_check(c, rules)) return rc == kEmptyLaunch ? G4D_OK : rc;
     const LinearArgs &in = c.in;
     const int mode = c.mode, nlayers = c.nlayers, K0 = in.K, *Kpad = c.Kpad, *Cout = c.Cout;
-    static const int xcd_swz = getenv("G4D_CHAIN_XCD") ? atoi(getenv("G4D_CHAIN_XCD")) : 1;          // A/B switch
+    static const int xcd_swz = env_int("G4D_CHAIN_XCD", 1);          // A/B switch
     ChainArgs s = {};
     s.in = kernel_in(c);
     if (c.unknown_grid) {
@@ -693,10 +693,10 @@ int g4d::mlp_chain_f32_run(const StackCall &c, hipStream_t st) {
     // registers, two per SIMD, one beside the FPS waves) gives 30.2k instead of 29.8k frames/s, so it is the default
     // (G4D_CHAIN_MT2_MIN_WAVES_WIDE=1024 restores the other choice).
     const long long waves32 = (c.rows + 31) / 32;
-    static const int mt_env = getenv("G4D_CHAIN_MT") ? atoi(getenv("G4D_CHAIN_MT")) : 0;  // tuning hook: 1 | 2
+    static const int mt_env = env_int("G4D_CHAIN_MT", 0);  // tuning hook: 1 | 2
     const bool wide = key >= 8000000;
-    static const long long mt2_min = getenv("G4D_CHAIN_MT2_MIN_WAVES") ? atoll(getenv("G4D_CHAIN_MT2_MIN_WAVES")) : 2048;      // tuning hooks
-    static const long long mt2_min_wide = getenv("G4D_CHAIN_MT2_MIN_WAVES_WIDE") ? atoll(getenv("G4D_CHAIN_MT2_MIN_WAVES_WIDE")) : 2048;
+    static const long long mt2_min = env_ll("G4D_CHAIN_MT2_MIN_WAVES", 2048);      // tuning hooks
+    static const long long mt2_min_wide = env_ll("G4D_CHAIN_MT2_MIN_WAVES_WIDE", 2048);
     const int mt = mt_env ? (mt_env >= 2 ? 2 : 1) : ((waves32 >= mt2_min || (wide && waves32 >= mt2_min_wide)) ? 2 : 1);
     if (g_group.active) {   // inside g4d_launch_group_begin / _end: the stack becomes a role of the group's launch
         G4D_REQUIRE(g_group.n < kMaxRoles, "g4d_launch_group: more than %d recorded launches", kMaxRoles);

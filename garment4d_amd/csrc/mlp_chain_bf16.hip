@@ -465,7 +465,7 @@ static int chain_bf16_impl(const StackCall &c, int nspl, hipStream_t st) {
         s.layer[l].kst = Kpad[l] / 32; s.layer[l].relu = c.relu[l]; s.layer[l].cout = Cout[l];
     }
     const long long waves32 = (c.rows + 31) / 32;
-    static const int mt_env = getenv("G4D_CHAIN_MT") ? atoi(getenv("G4D_CHAIN_MT")) : 0;
+    static const int mt_env = env_int("G4D_CHAIN_MT", 0);
     const bool wide = nspl == 3 && key >= 8000000;   // split mode: three weight pieces per fragment -> reuse them over 32 rows earlier
     const int mt = mt_env ? (mt_env >= 2 ? 2 : 1) : ((waves32 >= 2048 || (wide && waves32 >= 1024)) ? 2 : 1);
 #define G4D_CHAIN(T1, T2, T3, T4)                                                  \

@@ -1,7 +1,8 @@
 // Shared pieces of the MFMA shared-MLP kernels (mlp.hip: one layer per launch; mlp_stack.hip: up to four layers
 // per launch with activations resident in LDS): argument block, per-row loader state and the element loader of
 // the four A-operand sources (DIRECT / GROUP / INTERP / CSR) -- and, for the host side of the whole-stack launchers,
-// the call description they all take (StackCall) with the checks they share.
+// the call description they all take (StackCall) with the checks they share.  Also the one home of the epilogue / loader pieces that the
+// persistent kernels (sa_*.hip, fp_*.hip) share with them: pool4_rows_max, interp_weights.
 #pragma once
 #include "g4d_common.h"
 
@@ -64,6 +65,31 @@ __device__ __forceinline__ int out_row(const LinearArgs &a, int row) {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
+// max over the 16 rows of FOUR row-major tiles at once.  v_c (c = 0..3) holds, in lane (fi, fq), a value already reduced over that lane's
+// rows 4 fq + r; what is left is the max over the four 16-lane rows of the wave, per tile.  v_permlane16_swap(a, b) leaves
+// {a.row0, b.row0, a.row2, b.row2} / {a.row1, b.row1, a.row3, b.row3}, so ONE swap + ONE max halves two tiles at once and parks them in
+// alternating rows; v_permlane32_swap does the same for the two halves of the wave.  Result: lane 16 c + fi = max over all 16 rows of
+// tile c at column fi -- 64 different outputs in one register (one 256-byte store) after 3 swaps + 3 max, where reducing the tiles one by
+// one (lane_xor16 / lane_xor32: copies, swap, select, max per step) took ~40 instructions and four quarter-wave stores.
+__device__ __forceinline__ float pool4_rows_max(float v0, float v1, float v2, float v3) {
+    const auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v0), __float_as_uint(v1), false, false);
+    const auto b = __builtin_amdgcn_permlane16_swap(__float_as_uint(v2), __float_as_uint(v3), false, false);
+    const float m01 = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));   // rows: tile 0 (fq 0|1), tile 1 (fq 0|1), tile 0 (fq 2|3), tile 1 (fq 2|3)
+    const float m23 = fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
+    const auto c = __builtin_amdgcn_permlane32_swap(__float_as_uint(m01), __float_as_uint(m23), false, false);
+    return fmaxf(__uint_as_float(c[0]), __uint_as_float(c[1]));              // rows: tile 0, tile 1, tile 2, tile 3
+}
+
+// The inverse-distance weights of three_interpolate from the three squared distances of three_nn (pointnet2_utils.py:98 sqrt;
+// pointnet2_modules.py:140-142): a numerics contract -- these operations, each rounded, in this order -- that every kernel forming the
+// weights on the fly shares by calling this.
+struct InterpW { float w0, w1, w2; };
+__device__ __forceinline__ InterpW interp_weights(float d0, float d1, float d2) {
+    const float r0 = 1.0f / (__fsqrt_rn(d0) + 1e-8f), r1 = 1.0f / (__fsqrt_rn(d1) + 1e-8f), r2 = 1.0f / (__fsqrt_rn(d2) + 1e-8f);
+    const float norm = (r0 + r1) + r2;
+    return {r0 / norm, r1 / norm, r2 / norm};
+}
+
 // DIRECT launches with `tab` set (g4d_linear_interp_add_f32): the GEMM result of a row gets three_interpolate(tab) of that row added before the
 // affine -- the known-feature part of a feature-propagation level's first layer, pre-contracted over the m known rows (conv(sum_i w_i f_i) =
 // sum_i w_i conv(f_i); pointnet2_modules.py:139-149).  Weights as make_ctx<LOAD_INTERP> computes them; offsets in floats into `tab`.
@@ -73,9 +99,8 @@ __device__ __forceinline__ InterpRow interp_row(const LinearArgs &a, int row) {
     const int b = row / a.n;
     const int *ix = a.nn_idx + (size_t)row * 3;
     const float *d2 = a.dist2 + (size_t)row * 3;
-    const float r0 = 1.0f / (__fsqrt_rn(d2[0]) + 1e-8f), r1 = 1.0f / (__fsqrt_rn(d2[1]) + 1e-8f), r2 = 1.0f / (__fsqrt_rn(d2[2]) + 1e-8f);
-    const float norm = (r0 + r1) + r2;
-    c.w0 = r0 / norm; c.w1 = r1 / norm; c.w2 = r2 / norm;
+    const InterpW w = interp_weights(d2[0], d2[1], d2[2]);
+    c.w0 = w.w0; c.w1 = w.w1; c.w2 = w.w2;
     c.k0 = ((size_t)b * a.m + ix[0]) * a.tab_ld; c.k1 = ((size_t)b * a.m + ix[1]) * a.tab_ld; c.k2 = ((size_t)b * a.m + ix[2]) * a.tab_ld;
     return c;
 }
@@ -188,11 +213,8 @@ __device__ __forceinline__ RowCtx<MODE> make_ctx(const LinearArgs &a, int row) {
         const int b = row / a.n;
         const int *ix = a.nn_idx + (size_t)row * 3;
         const float *d2 = a.dist2 + (size_t)row * 3;
-        // pointnet2_utils.py:98 sqrt; pointnet2_modules.py:140-142 inverse-distance weights
-        const float r0 = 1.0f / (__fsqrt_rn(d2[0]) + 1e-8f), r1 = 1.0f / (__fsqrt_rn(d2[1]) + 1e-8f),
-                    r2 = 1.0f / (__fsqrt_rn(d2[2]) + 1e-8f);
-        const float norm = (r0 + r1) + r2;
-        c.w0 = r0 / norm; c.w1 = r1 / norm; c.w2 = r2 / norm;
+        const InterpW w = interp_weights(d2[0], d2[1], d2[2]);
+        c.w0 = w.w0; c.w1 = w.w1; c.w2 = w.w2;
         const size_t ks = (a.tab && a.C2 == 0) ? (size_t)a.tab_ld : (size_t)a.C2;   // register-chain kernel with an accumulator-init table: offsets into it
         c.k0 = ((size_t)b * a.m + ix[0]) * ks;
         c.k1 = ((size_t)b * a.m + ix[1]) * ks;

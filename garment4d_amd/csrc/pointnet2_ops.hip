@@ -6,6 +6,7 @@
 #include <cstdlib>
 
 #include "g4d_common.h"
+#include "mlp_common.h"
 #include "three_nn_body.h"
 
 namespace g4d {
@@ -153,7 +154,7 @@ __global__ void __launch_bounds__(256) three_nn_wide_kernel(int n, int m, const 
 // more wave time in total (every slice restarts its running third distance), and wave time is what the mix is short of.  So: split only
 // when the launch would leave SIMDs empty (fewer than 1024 waves un-split); G4D_NN_SPLIT = 1 | 2 | 4 overrides.
 static int nn_wide_split(long long queries) {
-    static const int v = [] { const char *e = getenv("G4D_NN_SPLIT"); return e ? atoi(e) : 0; }();
+    static const int v = env_int("G4D_NN_SPLIT", 0);
     if (v == 1 || v == 2 || v == 4) return v;
     return queries <= 65536 ? 4 : (queries <= 131072 ? 2 : 1);   // (round 4: throughput comes from coalesced calls of >= 1 M queries, un-split; a lone B = 8 step -- 65536 queries, one wave per SIMD un-split -- is a latency case)
 }
@@ -243,9 +244,8 @@ __global__ void __launch_bounds__(256) interp_concat_kernel(long long rows, int 
     const int b = (int)(row / n);
     const int *ix = nn_idx + row * 3;
     const float *d2 = dist2 + row * 3;
-    const float r0 = 1.0f / (__fsqrt_rn(d2[0]) + 1e-8f), r1 = 1.0f / (__fsqrt_rn(d2[1]) + 1e-8f), r2 = 1.0f / (__fsqrt_rn(d2[2]) + 1e-8f);
-    const float norm = (r0 + r1) + r2;
-    const float w0 = r0 / norm, w1 = r1 / norm, w2 = r2 / norm;
+    const InterpW w = interp_weights(d2[0], d2[1], d2[2]);
+    const float w0 = w.w0, w1 = w.w1, w2 = w.w2;
     const float *a0 = known + ((size_t)b * m + ix[0]) * C2, *a1 = known + ((size_t)b * m + ix[1]) * C2,
                 *a2 = known + ((size_t)b * m + ix[2]) * C2;
 #pragma unroll
@@ -363,7 +363,7 @@ extern "C" int g4d_three_nn_f32(int b, int n, int m, const float *unknown, const
     G4D_REQUIRE(b <= 65535, "g4d_three_nn_f32: b > 65535 not supported");
     if ((long long)b * n == 0) return G4D_OK;
     G4D_REQUIRE(unknown && dist2 && idx && (known || m == 0), "g4d_three_nn_f32: null pointer");
-    static const int wide_min_n = [] { const char *e = getenv("G4D_NN_WIDE_MIN_N"); return e ? atoi(e) : 4096; }();
+    static const int wide_min_n = env_int("G4D_NN_WIDE_MIN_N", 4096);
     if (n >= wide_min_n && m >= 256) {   // 64 queries per wave over the whole known set: see three_nn_wide_kernel
         G4D_NN_WIDE_LAUNCH(n, b, G4D_STREAM(stream), n, m, unknown, known, dist2, idx, (const unsigned char *)nullptr, (size_t)0, 0)
         return check_launch("g4d_three_nn_f32");

@@ -37,10 +37,6 @@ __device__ __forceinline__ float ldf(const float *base, unsigned elem) {
     return *reinterpret_cast<const float *>(reinterpret_cast<const char *>(base) + (elem << 2));
 }
 typedef float f32x3 __attribute__((ext_vector_type(3)));
-struct __attribute__((packed, aligned(4))) F3 { float x, y, z; };
-__device__ __forceinline__ F3 ldf3(const float *base, unsigned elem) {  // one 12-byte load: one cache-line lookup per row instead of three
-    return *reinterpret_cast<const F3 *>(reinterpret_cast<const char *>(base) + (elem << 2));
-}
 __device__ __forceinline__ f32x4 ldf4(const float *base, unsigned elem) {
     return *reinterpret_cast<const f32x4 *>(reinterpret_cast<const char *>(base) + (elem << 2));
 }
@@ -122,9 +118,9 @@ __global__ void __launch_bounds__(256, (PIPE && !TABLE && L1M && G4D_PE_PIPE_OCC
             if (E > 0) rw.e0[mt] = ldf(a.extra, src * E);
             if (E > 1) rw.c1[mt] = ldf(a.extra, src * E + (unsigned)min(1 + fq, E - 1));   // kk = 1 -> extra 1 + fq (0 beyond E)
         } else {
-            rw.px[mt] = ldf3(a.xyz, src * 3);
-            rw.pq[mt] = ldf3(a.new_xyz, (unsigned)qi * 3);
-            if (E == 3) rw.pe[mt] = ldf3(a.extra, src * 3);
+            rw.px[mt] = ld_f3(a.xyz, src * 3);
+            rw.pq[mt] = ld_f3(a.new_xyz, (unsigned)qi * 3);
+            if (E == 3) rw.pe[mt] = ld_f3(a.extra, src * 3);
             else {
 #pragma unroll
                 for (int e = 0; e < E; ++e) rw.ex[mt][e] = ldf(a.extra, src * E + e);
@@ -283,8 +279,8 @@ __global__ void __launch_bounds__(256, (PIPE && !TABLE && L1M && G4D_PE_PIPE_OCC
 
 template <bool TABLE, bool SBIG>
 static void launch_pe(int E, dim3 grid, hipStream_t st, const PeArgs &a) {
-    static const int pipe_env = getenv("G4D_PE_PIPE") ? atoi(getenv("G4D_PE_PIPE")) : -1;  // tuning hook: 0 | 1, default by variant
-    static const int l1m_env = getenv("G4D_PE_L1_MFMA") ? atoi(getenv("G4D_PE_L1_MFMA")) : 1;   // A/B switch: layer 1 on the matrix pipe (round 5)
+    static const int pipe_env = env_int("G4D_PE_PIPE", -1);  // tuning hook: 0 | 1, default by variant
+    static const int l1m_env = env_int("G4D_PE_L1_MFMA", 1);   // A/B switch: layer 1 on the matrix pipe (round 5)
     // round 4 measured the pipelined gathers at +10 % with a table and -17 % without (157 registers: three waves per SIMD instead of four).
     // With layer 1 on the matrix pipe the pipelined form without a table fits 128 registers (launch bounds: four waves per SIMD) and wins
     // there too: body encoders 901 / 446 / 241 -> 852 / 422 / 230 us at 240 frames x 4096 garment vertices, S = 32 / 16 / 8.

@@ -37,14 +37,6 @@ __device__ __forceinline__ uint4 pack8h(const f32x4 &a, const f32x4 &b) {
 __device__ __forceinline__ f32x4 mfma32h(const uint4 &a, const uint4 &b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
 }
-__device__ __forceinline__ float pool4_rows_max_h(float v0, float v1, float v2, float v3) {   // sa_xyz.hip: lane 16 c + fi = max over the 16 rows of tile c
-    const auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v0), __float_as_uint(v1), false, false);
-    const auto b = __builtin_amdgcn_permlane16_swap(__float_as_uint(v2), __float_as_uint(v3), false, false);
-    const float m01 = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
-    const float m23 = fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
-    const auto c = __builtin_amdgcn_permlane32_swap(__float_as_uint(m01), __float_as_uint(m23), false, false);
-    return fmaxf(__uint_as_float(c[0]), __uint_as_float(c[1]));
-}
 }  // namespace
 
 struct SaGrpHArgs {
@@ -245,9 +237,9 @@ __global__ void __launch_bounds__(64 * NW) sa_group_bf16_kernel(const SaGrpHArgs
             if constexpr (T3 >= 4) {
 #pragma unroll
                 for (int c4 = 0; c4 < T3 / 4; ++c4)
-                    o[c4 * 64 + lane] = fmaxf(pool4_rows_max_h(v[c4 * 4], v[c4 * 4 + 1], v[c4 * 4 + 2], v[c4 * 4 + 3]), 0.f);
+                    o[c4 * 64 + lane] = fmaxf(pool4_rows_max(v[c4 * 4], v[c4 * 4 + 1], v[c4 * 4 + 2], v[c4 * 4 + 3]), 0.f);
             } else {   // 32 output channels: two tiles, the upper half of the wave idles
-                const float m = fmaxf(pool4_rows_max_h(v[0], v[1], v[0], v[1]), 0.f);
+                const float m = fmaxf(pool4_rows_max(v[0], v[1], v[0], v[1]), 0.f);
                 if (lane < 32) o[lane] = m;
             }
         }
@@ -268,13 +260,7 @@ static int sa_group_bf16_launch(const SaGrpHArgs &a, hipStream_t st) {
         const int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(sa_group_bf16_kernel<T1, S, CIN, NW>), lds, attr, "g4d_sa_group_bf16");
         if (rc) return rc;
     }
-    static const int resident = [] {
-        int per_cu = 0, dev = 0;
-        hipDeviceProp_t prop;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, sa_group_bf16_kernel<T1, S, CIN, NW>, 64 * NW, lds) != hipSuccess || per_cu < 1) per_cu = 1;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess || prop.multiProcessorCount < 1) return per_cu * 256;
-        return per_cu * prop.multiProcessorCount;
-    }();
+    static const int resident = resident_workgroups(sa_group_bf16_kernel<T1, S, CIN, NW>, 64 * NW, lds);
     const long long nunit = a.rows / S;
     const long long want = (nunit + NW - 1) / NW;
     hipLaunchKernelGGL((sa_group_bf16_kernel<T1, S, CIN, NW>), dim3((unsigned)(want < resident ? want : resident)), dim3(64 * NW), lds, st, a);

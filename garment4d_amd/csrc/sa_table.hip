@@ -137,16 +137,6 @@ __global__ void __launch_bounds__(256) sa_units_items_kernel(int G, int nq_cap, 
     for (; n < cap; ++n) mine[n] = kItemDead;
 }
 
-
-__device__ __forceinline__ float pool4_rows_max_t(float v0, float v1, float v2, float v3) {   // sa_xyz.hip: lane 16 c + fi = max over the 16 rows of tile c
-    const auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v0), __float_as_uint(v1), false, false);
-    const auto b = __builtin_amdgcn_permlane16_swap(__float_as_uint(v2), __float_as_uint(v3), false, false);
-    const float m01 = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
-    const float m23 = fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
-    const auto c = __builtin_amdgcn_permlane32_swap(__float_as_uint(m01), __float_as_uint(m23), false, false);
-    return fmaxf(__uint_as_float(c[0]), __uint_as_float(c[1]));
-}
-
 constexpr int kStageK = 2;   // WM == 2: k-steps per staged chunk (one barrier per chunk)
 #ifndef G4D_SA64_OCC3
 #define G4D_SA64_OCC3 0   // experiment: the 64-wide, 32-sample stack (52 KB of LDS) at three workgroups per CU (<= 168 registers, 12 bytes of scratch): within 1 % on one box, off
@@ -506,7 +496,7 @@ __global__ void __launch_bounds__(256, (WM == 1 && C == 64 && S == 32 && G4D_SA6
                 const int g = blk * GP + mt;
 #pragma unroll
                 for (int c4 = 0; c4 < T3 / 4; ++c4) {
-                    const float m = fmaxf(pool4_rows_max_t(v[c4 * 4][mt], v[c4 * 4 + 1][mt], v[c4 * 4 + 2][mt], v[c4 * 4 + 3][mt]), 0.f);
+                    const float m = fmaxf(pool4_rows_max(v[c4 * 4][mt], v[c4 * 4 + 1][mt], v[c4 * 4 + 2][mt], v[c4 * 4 + 3][mt]), 0.f);
                     if (g < nq && live(it)) a.out[(size_t)g * a.ldo + a.col0 + c4 * 64 + lane] = m;
                 }
             }
@@ -542,8 +532,8 @@ __global__ void __launch_bounds__(256, (WM == 1 && C == 64 && S == 32 && G4D_SA6
 #pragma unroll
                 for (int c4 = 0; c4 < T3 / 4; ++c4) {
                     float m;
-                    if constexpr (G > 1) m = pool4_rows_max_t(pm[c4 * 4], pm[c4 * 4 + 1], pm[c4 * 4 + 2], pm[c4 * 4 + 3]);
-                    else m = pool4_rows_max_t(x[c4 * 4], x[c4 * 4 + 1], x[c4 * 4 + 2], x[c4 * 4 + 3]);
+                    if constexpr (G > 1) m = pool4_rows_max(pm[c4 * 4], pm[c4 * 4 + 1], pm[c4 * 4 + 2], pm[c4 * 4 + 3]);
+                    else m = pool4_rows_max(x[c4 * 4], x[c4 * 4 + 1], x[c4 * 4 + 2], x[c4 * 4 + 3]);
                     if (g < nq && live(it)) a.out[(size_t)g * a.ldo + a.col0 + c4 * 64 + lane] = fmaxf(m, 0.f);
                 }
             }
@@ -582,14 +572,7 @@ static int sa_table_launch(SaTabArgs a, hipStream_t st, void *ws = nullptr, long
         const int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(sa_table_kernel<C, S, MT, WM>), lds, attr, "g4d_sa_table");
         if (rc) return rc;
     }
-    static const int resident = [] {
-        const int lds = (int)sizeof(float) * (11 * C + (WLDS ? 3 * C * C : 0) + (WM == 2 ? 2 * kStageK * (C / 8) * 256 : 0));
-        int per_cu = 0, dev = 0;
-        hipDeviceProp_t prop;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, sa_table_kernel<C, S, MT, WM>, 256, lds) != hipSuccess || per_cu < 1) per_cu = 1;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess || prop.multiProcessorCount < 1) return per_cu * 256;
-        return per_cu * prop.multiProcessorCount;
-    }();
+    static const int resident = resident_workgroups(sa_table_kernel<C, S, MT, WM>, 256, lds);
     constexpr int R = 16 * MT, G = S > R ? S / R : 1;
     const long long nunit = ((a.rows + R - 1) / R + G - 1) / G;
     const long long want = (nunit + 3) / 4;

@@ -20,11 +20,9 @@
 // A pass = 32 rows (2 tiles): 96 MFMAs for [32, 32, 64].  Roofline: fp32 MFMA for the two contracted layers.
 #include <cstdlib>
 
-#include "g4d_common.h"
+#include "mlp_common.h"
 
 namespace g4d {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct SaXyzArgs {
     int n, p, S, logS, pool;          // pool: 1 max, 2 avg
@@ -39,26 +37,6 @@ struct SaXyzArgs {
     float *out;
     int ldo, col0;
 };
-
-struct __attribute__((packed, aligned(4))) F3s { float x, y, z; };
-__device__ __forceinline__ F3s ld3(const float *base, unsigned elem) {
-    return *reinterpret_cast<const F3s *>(reinterpret_cast<const char *>(base) + (elem << 2));
-}
-
-// max over the 16 rows of FOUR row-major tiles at once.  v_c (c = 0..3) holds, in lane (fi, fq), a value already reduced over that lane's
-// rows 4 fq + r; what is left is the max over the four 16-lane rows of the wave, per tile.  v_permlane16_swap(a, b) leaves
-// {a.row0, b.row0, a.row2, b.row2} / {a.row1, b.row1, a.row3, b.row3}, so ONE swap + ONE max halves two tiles at once and parks them in
-// alternating rows; v_permlane32_swap does the same for the two halves of the wave.  Result: lane 16 c + fi = max over all 16 rows of
-// tile c at column fi -- 64 different outputs in one register (one 256-byte store) after 3 swaps + 3 max, where reducing the tiles one by
-// one (lane_xor16 / lane_xor32: copies, swap, select, max per step) took ~40 instructions and four quarter-wave stores.
-__device__ __forceinline__ float pool4_rows_max(float v0, float v1, float v2, float v3) {
-    const auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v0), __float_as_uint(v1), false, false);
-    const auto b = __builtin_amdgcn_permlane16_swap(__float_as_uint(v2), __float_as_uint(v3), false, false);
-    const float m01 = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));   // rows: tile 0 (fq 0|1), tile 1 (fq 0|1), tile 0 (fq 2|3), tile 1 (fq 2|3)
-    const float m23 = fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
-    const auto c = __builtin_amdgcn_permlane32_swap(__float_as_uint(m01), __float_as_uint(m23), false, false);
-    return fmaxf(__uint_as_float(c[0]), __uint_as_float(c[1]));              // rows: tile 0, tile 1, tile 2, tile 3
-}
 
 // One stack over the passes `first, first + stride, ...` of a wave (a pass = 32 consecutive grouped rows).  LOGS / MAXP are compile-time:
 // with the pooling mode and window resolved at run time the epilogue was ~45 % of the loop's VALU instructions (both max and sum

@@ -37,26 +37,6 @@ namespace {
 constexpr int kPrM = 1024;          // known points per cloud, padded
 constexpr int kPrBlk = 16;          // records per block
 constexpr int kPrNB = kPrM / kPrBlk;   // 64 blocks: one per lane
-
-__device__ __forceinline__ unsigned pr_part1by2(unsigned v) {
-    v &= 0x3ffu;
-    v = (v | (v << 16)) & 0x030000ffu;
-    v = (v | (v << 8)) & 0x0300f00fu;
-    v = (v | (v << 4)) & 0x030c30c3u;
-    v = (v | (v << 2)) & 0x09249249u;
-    return v;
-}
-
-__device__ __forceinline__ float pr_wave_min(float v) {   // NaN-safe (fminf drops a NaN), all lanes end with the result
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ float pr_wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
 }  // namespace
 
 // workspace per cloud: kPrM float4 records (sorted; padding: +inf coordinates, index INT_MAX) + kPrNB boxes of 8 floats (lo.xyz, 0, hi.xyz, 0)
@@ -82,8 +62,8 @@ __global__ void __launch_bounds__(kPrepT) nn_prune_prep_kernel(int m, const floa
             hx = fmaxf(hx, x); hy = fmaxf(hy, y); hz = fmaxf(hz, z);
         }
     }
-    lx = pr_wave_min(lx); ly = pr_wave_min(ly); lz = pr_wave_min(lz);
-    hx = pr_wave_max(hx); hy = pr_wave_max(hy); hz = pr_wave_max(hz);
+    lx = wave_min_all(lx); ly = wave_min_all(ly); lz = wave_min_all(lz);
+    hx = wave_max_all(hx); hy = wave_max_all(hy); hz = wave_max_all(hz);
     if (lane == 0) { red[0][wave] = lx; red[1][wave] = ly; red[2][wave] = lz; red[3][wave] = hx; red[4][wave] = hy; red[5][wave] = hz; }
     __syncthreads();
 #pragma unroll
@@ -101,7 +81,7 @@ __global__ void __launch_bounds__(kPrepT) nn_prune_prep_kernel(int m, const floa
             const unsigned cx = (unsigned)fminf(fmaxf((x - lx) * scale, 0.f), 1023.f);
             const unsigned cy = (unsigned)fminf(fmaxf((y - ly) * scale, 0.f), 1023.f);
             const unsigned cz = (unsigned)fminf(fmaxf((z - lz) * scale, 0.f), 1023.f);
-            const unsigned code = pr_part1by2(cx) | (pr_part1by2(cy) << 1) | (pr_part1by2(cz) << 2);
+            const unsigned code = part1by2(cx) | (part1by2(cy) << 1) | (part1by2(cz) << 2);
             key = ((unsigned long long)code << 32) | (unsigned)k;
         }
         keys[k] = key;
@@ -199,7 +179,7 @@ __global__ void __launch_bounds__(kPrT) three_nn_prune_kernel(int n, int m, cons
         const float gx = sgrid[0], gy = sgrid[1], gz = sgrid[2], gs = sgrid[3];
         const unsigned cx = (unsigned)fminf(fmaxf((ux - gx) * gs, 0.f), 1023.f), cy = (unsigned)fminf(fmaxf((uy - gy) * gs, 0.f), 1023.f),
                        cz = (unsigned)fminf(fmaxf((uz - gz) * gs, 0.f), 1023.f);
-        const unsigned cq = pr_part1by2(cx) | (pr_part1by2(cy) << 1) | (pr_part1by2(cz) << 2);
+        const unsigned cq = part1by2(cx) | (part1by2(cy) << 1) | (part1by2(cz) << 2);
         int pos = 0;
 #pragma unroll
         for (int step = kPrNB / 2; step > 0; step >>= 1)
@@ -213,13 +193,13 @@ __global__ void __launch_bounds__(kPrT) three_nn_prune_kernel(int n, int m, cons
         }
     }
     // ---- 2. the walk: ascending over the blocks that can still matter to some lane
-    const float qlx = pr_wave_min(ux), qly = pr_wave_min(uy), qlz = pr_wave_min(uz);   // the wave's query box (NaN coordinates dropped)
-    const float qhx = pr_wave_max(ux), qhy = pr_wave_max(uy), qhz = pr_wave_max(uz);
+    const float qlx = wave_min_all(ux), qly = wave_min_all(uy), qlz = wave_min_all(uz);   // the wave's query box (NaN coordinates dropped)
+    const float qhx = wave_max_all(ux), qhy = wave_max_all(uy), qhz = wave_max_all(uz);
     const float *mybox = sbox + min(lane, kPrNB - 1) * 8;
     // lane l: lower bound of d(query, point) over every query of the wave and every point of block l
     const float wbound = dist2<FM>(pr_gap(mybox[0], mybox[4], qlx, qhx), pr_gap(mybox[1], mybox[5], qly, qhy), pr_gap(mybox[2], mybox[6], qlz, qhz));
     const bool nanq = !(ux == ux && uy == uy && uz == uz);   // a NaN query inserts nothing (inf / 0 like in the scan): it asks for no block
-    const float maxb3 = pr_wave_max(nanq ? -INF : b3);
+    const float maxb3 = wave_max_all(nanq ? -INF : b3);
     unsigned long long rest = __builtin_amdgcn_ballot_w64(lane < nblk && !(wbound > maxb3));   // (NaN bounds -- infinite coordinates on both sides -- are kept)
     for (; rest != 0ull; rest &= rest - 1) {
         const int blk = __builtin_ctzll(rest);
