@@ -3,7 +3,9 @@ and return type (smplx/smplx/body_models.py:44-478), `VertexJointSelector`
 (smplx/smplx/vertex_joint_selector.py:28-77), and `smpl_clip_batch` -- the three body evaluations per frame (posed,
 T-pose, zero-pose) that the reference's data loader runs one frame at a time on the CPU
 (utils/dataloader.py:186-246), done for all frames of a batch in three batched launches on the GPU, returned under the
-reference's batch keys.  SURVEY.md section 8f rank 3.  Forward only; `lbs()` is garment4d_amd.lbs.lbs (csrc/lbs.hip)."""
+reference's batch keys.  SURVEY.md section 8f rank 3.  `lbs()` is garment4d_amd.lbs.lbs (csrc/lbs.hip).  Forward only, under no_grad, unless
+tuning.Tuning.lbs_autograd is on and grad is enabled: then SMPL / SMPLLayer.forward keep the graph from betas, body_pose, global_orient and transl
+(passed in or the module's own parameters) to the vertices and joints -- lbs()'s adjoint on HIP, the rest torch's own ops."""
 import os
 import pickle
 from dataclasses import dataclass, fields
@@ -14,6 +16,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from . import tuning
 from .lbs import batch_rodrigues, lbs
 
 # smplx/smplx/vertex_ids.py:24-46 -- SMPL / SMPL+H vertex numbers of the extra (face, feet, finger-tip) key points
@@ -71,6 +74,11 @@ class SMPLOutput(ModelOutput):
     body_pose: Optional[torch.Tensor] = None
 
 
+def _lbs_graph():
+    """True when a body model's forward keeps its autograd graph: the opt-in is on and the caller has grad enabled."""
+    return tuning.current().lbs_autograd and torch.is_grad_enabled()
+
+
 class VertexJointSelector(nn.Module):
     def __init__(self, vertex_ids=None, use_hands=True, use_feet_keypoints=True, **kwargs):
         super().__init__()
@@ -89,6 +97,11 @@ class VertexJointSelector(nn.Module):
         vertex: it is kept inside the buffer for the gather and its joint is NaN (the reference's index_select would raise)."""
         B, V, _ = vertices.shape
         E = self.extra_joints_idxs.numel()
+        if torch.is_grad_enabled() and (vertices.requires_grad or joints.requires_grad):   # (tuning.lbs_autograd: the same selection as torch ops)
+            extra = vertices[:, self.extra_joints_idxs.clamp_max(max(V - 1, 0))]
+            if self._max_idx >= V:
+                extra = extra.masked_fill((self.extra_joints_idxs >= V).view(1, E, 1), float("nan"))
+            return torch.cat([joints, extra], dim=1)
         out = torch.empty((B, joints.shape[1] + E, 3), dtype=torch.float32, device=vertices.device)
         out[:, :joints.shape[1]] = joints
         ids = self.extra_joints_idxs
@@ -182,9 +195,15 @@ class SMPL(nn.Module):
         return SMPLOutput(vertices=vertices if return_verts else None, global_orient=global_orient, body_pose=body_pose, joints=joints,
                           betas=betas, full_pose=full_pose if return_full_pose else None)
 
-    @torch.no_grad()
     def forward(self, betas=None, body_pose=None, global_orient=None, transl=None, return_verts=True, return_full_pose=False,
                 pose2rot=True, **kwargs):
+        """no_grad, as the reference's data loader runs it -- unless tuning.Tuning.lbs_autograd is on and grad is enabled (SMPLLayer too)."""
+        with torch.enable_grad() if _lbs_graph() else torch.no_grad():
+            return self._forward(betas=betas, body_pose=body_pose, global_orient=global_orient, transl=transl, return_verts=return_verts,
+                                 return_full_pose=return_full_pose, pose2rot=pose2rot, **kwargs)
+
+    def _forward(self, betas=None, body_pose=None, global_orient=None, transl=None, return_verts=True, return_full_pose=False,
+                 pose2rot=True, **kwargs):
         """body_models.py:287-371: axis-angle pose (B,69) + global_orient (B,3) (member variables when not given)."""
         global_orient = global_orient if global_orient is not None else self.global_orient
         body_pose = body_pose if body_pose is not None else self.body_pose
@@ -204,9 +223,8 @@ class SMPLLayer(SMPL):
     def __init__(self, *args, **kwargs):
         super().__init__(*args, create_body_pose=False, create_betas=False, create_global_orient=False, create_transl=False, **kwargs)
 
-    @torch.no_grad()
-    def forward(self, betas=None, body_pose=None, global_orient=None, transl=None, return_verts=True, return_full_pose=False,
-                pose2rot=True, **kwargs):
+    def _forward(self, betas=None, body_pose=None, global_orient=None, transl=None, return_verts=True, return_full_pose=False,
+                 pose2rot=True, **kwargs):
         """body_models.py:391-478: rotation-matrix inputs -- global_orient (B,1,3,3) / (B,3,3), body_pose (B,23,3,3)."""
         batch_size = 1
         for var in (betas, global_orient, body_pose, transl):

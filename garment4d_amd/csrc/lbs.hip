@@ -15,6 +15,7 @@
 #include <cstdlib>
 
 #include "g4d_common.h"
+#include "smpl_rigid.h"   // rodrigues(), wave_sync_lds(): shared with smpl/smpl_grad.hip
 
 namespace g4d {
 
@@ -64,25 +65,6 @@ __global__ void __launch_bounds__(256) joint_regress_kernel(int J, int V, long l
         const int c = threadIdx.x;
         joints[((size_t)b * J + j) * 3 + c] = (red[0][c] + red[1][c]) + (red[2][c] + red[3][c]);
     }
-}
-
-// lbs.py:312-346  batch_rodrigues: angle = ||r + 1e-8||, dir = r / angle, R = I + sin K + (1 - cos) K K
-__device__ __forceinline__ void rodrigues(float rx, float ry, float rz, float *R) {
-    const float ax = rx + 1e-8f, ay = ry + 1e-8f, az = rz + 1e-8f;
-    const float angle = __fsqrt_rn(ax * ax + ay * ay + az * az);
-    const float x = rx / angle, y = ry / angle, z = rz / angle;
-    const float s = sinf(angle), c1 = 1.0f - cosf(angle);
-    // K = [[0,-z,y],[z,0,-x],[-y,x,0]];  K K = [[-(y2+z2), xy, xz],[xy, -(x2+z2), yz],[xz, yz, -(x2+y2)]]
-    const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, xz = x * z, yz = y * z;
-    R[0] = 1.0f + c1 * (-(zz + yy));  // row-major 3x3; K K[0][0] = -z*z - y*y (bmm order: (-z)(z) + (y)(-y))
-    R[1] = s * (-z) + c1 * xy;
-    R[2] = s * y + c1 * xz;
-    R[3] = s * z + c1 * xy;
-    R[4] = 1.0f + c1 * (-(zz + xx));
-    R[5] = s * (-x) + c1 * yz;
-    R[6] = s * (-y) + c1 * xz;
-    R[7] = s * x + c1 * yz;
-    R[8] = 1.0f + c1 * (-(yy + xx));
 }
 
 __global__ void __launch_bounds__(256) rodrigues_kernel(int n, const float *__restrict__ rv, float *__restrict__ out) {
@@ -275,12 +257,6 @@ constexpr int kOneRows = 28;  // blend rows per slice held in registers (8 x 28 
 constexpr int kOneJ = 32;     // joints
 typedef float lbs_f4 __attribute__((ext_vector_type(4)));
 }  // namespace
-
-__device__ __forceinline__ void wave_sync_lds() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 __global__ void __launch_bounds__(64 * kOneKS) lbs_one_kernel(int B, int V, int J, int NB, int pose2rot, const float *__restrict__ betas,
                                                               int betas_bstride, const float *__restrict__ pose,

@@ -4,9 +4,11 @@ batch_rodrigues :312, batch_rigid_transform :362), computed by the HIP kernels o
 
 The reference evaluates these on the CPU, batch 1, three times per frame inside DataLoader workers
 (utils/dataloader.py:199-212) and again on the GPU for the garment skinning (modules/mesh_encoder.py:333-408).
-Here one call handles the whole batch of frames.  Forward only (the reference never differentiates through
+Here one call handles the whole batch of frames.  Forward only by default (the reference never differentiates through
 the body model: it runs under no_grad in the dataloader; the garment path's gradient flows through torch ops
-that remain available in the reference's own lbs.py).
+that remain available in the reference's own lbs.py).  Opt-in (tuning.Tuning.lbs_autograd): lbs() of a grad-requiring
+betas or pose returns its outputs with a graph whose backward is lbs_backward(), the adjoint kernels of
+csrc/smpl/smpl_grad.hip (include/g4d_smpl.h) -- what registering the body to a scan needs (body_fit.py).
 """
 import torch
 
@@ -142,10 +144,81 @@ def skin(weights, A, verts, group=1):
     return out
 
 
+def lbs_backward(betas, pose, v_template, shapedirs, posedirs, J_regressor, parents, lbs_weights, d_verts, d_joints, pose2rot: bool = True):
+    """The adjoint of lbs() (g4d_smpl_lbs_grad_f32): d_verts (B,V,3) and d_joints (B,J,3), either None (zero), -> (d_betas, d_pose) in the shapes
+    of betas and pose.  betas of one row with B > 1 frames: d_betas is the sum over the frames, in ascending frame order.  Nothing of the forward
+    is kept: the kernels recompute it from betas, pose and the constants.  No atomics, no host round trip (after one eager call, which prepares
+    the model constants, the call can be captured in a hipGraph).  Domain: J <= 32 and NB + 9 (J - 1) <= 224, else G4DError before any launch."""
+    betas, pose = _f32(betas.detach(), "betas"), _f32(pose.detach(), "pose")
+    v_template, shapedirs, posedirs = _f32(v_template, "v_template"), _f32(shapedirs, "shapedirs"), _f32(posedirs, "posedirs")
+    J_regressor, lbs_weights = _f32(J_regressor, "J_regressor"), _f32(lbs_weights, "lbs_weights")
+    if v_template.dim() == 3:
+        if v_template.shape[0] != 1:
+            raise NotImplementedError("per-sample v_template is not supported by the HIP path")
+        v_template = v_template[0].contiguous()
+    B, V, NB, J, dev = pose.shape[0], v_template.shape[0], betas.shape[1], J_regressor.shape[0], betas.device
+    _require(betas.shape[0] in (1, B), "lbs_backward: betas batch must be 1 or equal to the pose batch")
+    _require(pose.numel() == B * J * (3 if pose2rot else 9), f"lbs_backward: pose has {pose.numel()} elements, expected B*J*{3 if pose2rot else 9}")
+    _require(posedirs.dim() == 2 and posedirs.shape[0] == (J - 1) * 9 and posedirs.shape[1] == V * 3, "lbs_backward: posedirs must be ((J-1)*9, V*3)")
+    _require(tuple(shapedirs.shape) == (V, 3, NB) and tuple(J_regressor.shape) == (J, V) and tuple(lbs_weights.shape) == (V, J) and len(parents) == J,
+             "lbs_backward: the model constants do not match each other")
+    gv = gj = None
+    if d_verts is not None:
+        gv = _f32(d_verts.detach(), "d_verts")
+        _require(tuple(gv.shape) == (B, V, 3), f"lbs_backward: d_verts {tuple(gv.shape)} must be (B={B}, V={V}, 3)")
+    if d_joints is not None:
+        gj = _f32(d_joints.detach(), "d_joints")
+        _require(tuple(gj.shape) == (B, J, 3), f"lbs_backward: d_joints {tuple(gj.shape)} must be (B={B}, J={J}, 3)")
+    L = _lib.smpl_lib()[0]
+    blend_dirs, Jt, Js = _model_constants(v_template, shapedirs, posedirs, J_regressor)
+    d_pose = torch.zeros(pose.shape, dtype=torch.float32, device=dev)
+    d_betas = torch.zeros(betas.shape, dtype=torch.float32, device=dev)
+    nws = int(L.g4d_smpl_grad_ws_bytes(B, V, J, NB))
+    if nws < 0:
+        raise _lib.G4DError(f"lbs_backward: J={J}, NB={NB} is outside the domain of g4d_smpl_lbs_grad_f32 (J <= 32, NB + 9 (J - 1) <= 224)")
+    ws = _lib.workspace(nws, dev)
+    _lib.call("g4d_smpl_lbs_grad_f32", B, V, J, NB, int(bool(pose2rot)), betas.data_ptr(), NB if betas.shape[0] == B else 0, pose.data_ptr(),
+              v_template.data_ptr(), blend_dirs.data_ptr(), Jt.data_ptr(), Js.data_ptr(), _parents_i32(parents, dev).data_ptr(), lbs_weights.data_ptr(),
+              gv.data_ptr() if gv is not None else None, gj.data_ptr() if gj is not None else None, d_pose.data_ptr(), d_betas.data_ptr(),
+              ws.data_ptr(), nws, _lib.stream_ptr())
+    return d_betas, d_pose
+
+
+class _LbsFn(torch.autograd.Function):
+    """(verts, posed joints) = the inference route's own call (the same bits); backward = lbs_backward.  Only its inputs are saved."""
+
+    @staticmethod
+    def forward(ctx, betas, pose, consts, pose2rot):
+        with torch.no_grad():
+            verts, posed = _lbs_forward(betas, pose, *consts, pose2rot=pose2rot)
+        ctx.save_for_backward(betas, pose)
+        ctx.consts, ctx.pose2rot = consts, pose2rot
+        ctx.set_materialize_grads(False)   # an unused output arrives as None (the kernel's NULL), not as a tensor of zeros
+        return verts, posed
+
+    @staticmethod
+    def backward(ctx, d_verts, d_joints):
+        betas, pose = ctx.saved_tensors
+        d_betas, d_pose = lbs_backward(betas, pose, *ctx.consts, d_verts, d_joints, pose2rot=ctx.pose2rot)
+        return (d_betas if ctx.needs_input_grad[0] else None), (d_pose if ctx.needs_input_grad[1] else None), None, None
+
+
 def lbs(betas, pose, v_template, shapedirs, posedirs, J_regressor, parents, lbs_weights, pose2rot: bool = True):
     """Linear blend skinning.  betas (B,NB); pose (B,(J)*3) axis-angle if pose2rot else rotation matrices
     (B,J,3,3) / (B,J*9); v_template (V,3); shapedirs (V,3,NB); posedirs ((J-1)*9, V*3); J_regressor (J,V);
-    parents (J); lbs_weights (V,J).  Returns (verts (B,V,3), posed joints (B,J,3))."""
+    parents (J); lbs_weights (V,J).  Returns (verts (B,V,3), posed joints (B,J,3)).
+    Under tuning.Tuning.lbs_autograd, with grad enabled and betas or pose requiring grad, the two are outputs of one autograd.Function (the
+    same call, the same bits) whose backward is lbs_backward(); a model constant that requires grad then raises NotImplementedError."""
+    if _T().lbs_autograd and torch.is_grad_enabled() and isinstance(betas, torch.Tensor) and isinstance(pose, torch.Tensor):
+        consts = (v_template, shapedirs, posedirs, J_regressor, parents, lbs_weights)
+        if any(isinstance(c, torch.Tensor) and c.requires_grad for c in consts):
+            raise NotImplementedError("lbs: gradients to the model constants (v_template, shapedirs, posedirs, J_regressor, lbs_weights) are not implemented")
+        if betas.requires_grad or pose.requires_grad:
+            return _LbsFn.apply(betas, pose, consts, bool(pose2rot))
+    return _lbs_forward(betas, pose, v_template, shapedirs, posedirs, J_regressor, parents, lbs_weights, pose2rot=pose2rot)
+
+
+def _lbs_forward(betas, pose, v_template, shapedirs, posedirs, J_regressor, parents, lbs_weights, pose2rot: bool = True):
     betas, pose = _f32(betas, "betas"), _f32(pose, "pose")
     v_template, shapedirs, posedirs = _f32(v_template, "v_template"), _f32(shapedirs, "shapedirs"), _f32(posedirs, "posedirs")
     J_regressor, lbs_weights = _f32(J_regressor, "J_regressor"), _f32(lbs_weights, "lbs_weights")
