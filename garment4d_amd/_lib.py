@@ -12,7 +12,8 @@ Further libraries of the package are (header, library) pairs of the same shape, 
 lib/libg4d_render.so (render_lib(); record: tests/render_abi_snapshot.txt), and the virtual depth-sensor scans, include/g4d_scan.h +
 lib/libg4d_scan.so (scan_lib(); record: tests/scan_abi_snapshot.txt), and the point-to-surface loss, include/g4d_fit.h + lib/libg4d_fit.so
 (fit_lib(); record: tests/fit_abi_snapshot.txt), and the adjoint of lbs(), include/g4d_smpl.h + lib/libg4d_smpl.so (smpl_lib(); record:
-tests/smpl_abi_snapshot.txt).  call() serves them too.  include/g4d_sets.h is a further header of
+tests/smpl_abi_snapshot.txt), and the adjoint of the garment skinning, include/g4d_skin.h + lib/libg4d_skin.so (skin_lib(); record:
+tests/skin_abi_snapshot.txt).  call() serves them too.  include/g4d_sets.h is a further header of
 libg4d_hip.so ITSELF (sets_lib(); record: tests/sets_abi_snapshot.txt): entry points added after g4d.h's record was closed.
 """
 import ctypes
@@ -37,6 +38,9 @@ FIT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "g4d_fit.h")
 # the fifth pair: the adjoint of lbs() (include/g4d_smpl.h, libg4d_smpl.so; smpl_lib() loads it)
 SMPL_LIB_PATH = os.path.join(_HERE, "lib", "libg4d_smpl.so")
 SMPL_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "g4d_smpl.h")
+# the sixth pair: the adjoint of the garment skinning (include/g4d_skin.h, libg4d_skin.so; skin_lib() loads it)
+SKIN_LIB_PATH = os.path.join(_HERE, "lib", "libg4d_skin.so")
+SKIN_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "g4d_skin.h")
 
 # a further header of libg4d_hip.so itself (no library of its own): entry points that came after the record of g4d.h (sets_lib() binds them)
 SETS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "g4d_sets.h")
@@ -201,6 +205,11 @@ def fit_lib():
 def smpl_lib():
     """libg4d_smpl.so typed from include/g4d_smpl.h: (CDLL, prototypes, constants)."""
     return load_pair(SMPL_HEADER_PATH, SMPL_LIB_PATH)
+
+
+def skin_lib():
+    """libg4d_skin.so typed from include/g4d_skin.h: (CDLL, prototypes, constants)."""
+    return load_pair(SKIN_HEADER_PATH, SKIN_LIB_PATH)
 
 
 def sets_lib():

@@ -5,6 +5,7 @@
 // Both HBM/L2-bound gathers with point-major rows; nothing is repeated/expanded the way the reference does it
 // (`.repeat(1, 1, K, 1)` of the (V, J) weight table followed by torch.gather materialises B*T x Vg x K x J floats).
 #include "g4d_common.h"
+#include "knn_blend_weights.h"
 
 namespace g4d {
 
@@ -26,26 +27,7 @@ __global__ void __launch_bounds__(256) knn_blend_weights_kernel(long long rows, 
     const long long c = f / frames_per_clip;
     const int *ix = idx + ((size_t)c * vg + gv) * K;
     const float *dd = dists + ((size_t)c * vg + gv) * K;
-    int iv[4];
-    float wv[4];
-    float s = 0.f;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const int k = q * 64 + lane;
-        iv[q] = k < K ? ix[k] : 0;
-        float w = k < K ? 1.0f / dd[k] : 0.f;
-        if (__builtin_isinf(w)) w = 0.f;
-        wv[q] = w;
-        s += w;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        float w = wv[q] / s;
-        if (__builtin_isinf(w)) w = 0.f;
-        wv[q] = w;
-    }
+    G4D_KNN_BLEND_LANE_WEIGHTS(ix, dd, K, lane)   // iv[4], wv[4], s -- knn_blend_weights.h: shared with the adjoint (skin/skin_grad.hip)
     const float *Wf = W + (size_t)f * v * J;
     const int half = HALVES == 2 ? lane >> 5 : 0;
     const int j = HALVES == 2 ? lane & 31 : lane;

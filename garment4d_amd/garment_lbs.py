@@ -6,8 +6,8 @@ symmetrised garment-mesh adjacency, :299-303) are passed explicitly because this
 Differences that do not change results: ONE K-nearest search serves the K, min(64,K) and K=1 queries of :321-324 (the
 sorted K=256 list contains the others as prefixes); the (V,J) weight table is never `.repeat`-ed K times -- the blend
 kernel gathers rows; the per-frame weights are blended with the clip's neighbour list without materialising the
-(B*T, Vg, K, J) tensor of :381-382.  Forward only -- except lbs_garment_MGN (the MGN variant's nearest-vertex skinning), which is
-differentiable in the garment (csrc/mgn_skin_grad.hip).
+(B*T, Vg, K, J) tensor of :381-382.  Differentiable in the garment alone: lbs_garment_MGN (the MGN variant's nearest-vertex skinning,
+csrc/mgn_skin_grad.hip) always, lbs_garment_interpolation behind tuning.Tuning.garment_lbs_autograd (csrc/skin/skin_grad.hip).
 """
 import numpy as np
 import torch
@@ -17,6 +17,7 @@ from . import _lib
 from . import grad_ops
 from . import lbs as L
 from . import mesh_tables
+from . import tuning
 from .gcn import normalize
 from .knn import KNN, knn_points
 
@@ -73,19 +74,37 @@ def _smoothing_csr(adj_old, device):
     return _cache.by_identity(_smooth_csr_cache, 8, (adj_old,), str(device), build)
 
 
-def smooth_weights(nn_W, adj_old, coeff=0.1, iters=100, method=None):
+_smooth_csr_t_cache = {}
+
+
+def _smoothing_csr_t(adj_old, device):
+    """_smoothing_csr of the TRANSPOSED operator (D^-1 A - I)^T, cached the same way: what the adjoint of the smoothing walks.  A is symmetric in
+    its pattern, so the rows have the lengths of the forward operator's and the same kernels serve (row u lists the v with an entry (v, u),
+    ascending: mesh_tables.transposed)."""
+    def build():
+        import scipy.sparse as sp
+        m = mesh_tables.transposed(mesh_tables.sorted_csr(sp.csr_matrix(normalize(adj_old) - sp.eye(adj_old.shape[0]))))
+        return mesh_tables.csr_tensors(m, device) + (m.shape[0], mesh_tables.longest_row(m))
+
+    return _cache.by_identity(_smooth_csr_t_cache, 8, (adj_old,), str(device), build)
+
+
+def smooth_weights(nn_W, adj_old, coeff=0.1, iters=100, method=None, transpose=False):
     """100 Jacobi steps  W <- W + coeff * ((D^-1 A - I) . W)  over the garment mesh (:385-390).
     method "jacobi": the steps as written, one SpMM-axpy kernel each (ping-pong buffers).
     method "fused" (default when the mesh fits: mesh_tables.MAX_VG vertices, MAX_ROW entries per adjacency row): all steps in ONE hand-written launch,
     the weights of a (frame, 4-joint slab) resident in LDS (g4d_jacobi_smooth_f32) -- bit-identical to "jacobi".
     method "operator": the same linear map applied as one dense fp32 matrix product (see smoothing_operator; a LIBRARY GEMM,
-    kept as a cross-check only); differs from the step-by-step result only by rounding.  G4D_SMOOTH overrides the default."""
+    kept as a cross-check only); differs from the step-by-step result only by rounding.  G4D_SMOOTH overrides the default.
+    transpose=True: the steps of the transposed operator, W <- W + coeff * ((D^-1 A - I)^T . W) -- the adjoint of the smoothing, which is linear
+    (the same launches, given _smoothing_csr_t)."""
     import os
     F_, Vg, J = nn_W.shape
     import scipy.sparse as sp
     method = method or os.environ.get("G4D_SMOOTH") or "fused"
+    csr = _smoothing_csr_t if transpose else _smoothing_csr
     if method == "fused":
-        rowptr, colidx, vals, n, max_row = _smoothing_csr(adj_old, nn_W.device)
+        rowptr, colidx, vals, n, max_row = csr(adj_old, nn_W.device)
         assert n == Vg
         if Vg <= mesh_tables.MAX_VG and max_row <= mesh_tables.MAX_ROW:
             x = nn_W.contiguous()
@@ -96,10 +115,11 @@ def smooth_weights(nn_W, adj_old, coeff=0.1, iters=100, method=None):
         method = "jacobi"   # mesh too large / too irregular for the LDS-resident kernel: one launch per step
     if method == "operator":
         M = smoothing_operator(adj_old, coeff, iters, nn_W.device)
+        M = M.t().contiguous() if transpose else M
         x = nn_W.permute(1, 0, 2).reshape(Vg, F_ * J)                      # vertex-major view of all frames / joints
         return torch.mm(M, x).view(Vg, F_, J).permute(1, 0, 2).contiguous()   # plain library GEMM
     assert method == "jacobi", method
-    rowptr, colidx, vals, n, _ = _smoothing_csr(adj_old, nn_W.device)
+    rowptr, colidx, vals, n, _ = csr(adj_old, nn_W.device)
     assert n == Vg
     a, b, spare = nn_W.contiguous(), torch.empty_like(nn_W), None   # the caller's tensor is read, never written
     st = _lib.stream_ptr()
@@ -117,7 +137,32 @@ def lbs_garment_interpolation(pred_template_garment_v, Tpose_vertices, Tpose_roo
                               T_J_regressor, T_lbs_weights, adj_old, K=3, clip_J_regressor=None, clip_lbs_weights=None):
     """pred_template_garment_v (B,Vg,3); Tpose_vertices (B,[1,]V,3); Tpose_root_joints (B,[1,]3); zeropose_vertices (B,T,V,3);
     gt_pose (B,T,72); T_J_regressor (B,T,J,V); T_lbs_weights (B,T,V,J); adj_old scipy sparse (Vg,Vg).
-    Returns (posed garment (B,T,Vg,3), nearest-neighbour KNN (K=1), un-posed garment repeated over T (B,T,Vg,3))."""
+    Returns (posed garment (B,T,Vg,3), nearest-neighbour KNN (K=1), un-posed garment repeated over T (B,T,Vg,3)).
+    Under tuning.Tuning.garment_lbs_autograd, with grad enabled and a grad-requiring first argument, the posed and the un-posed garment carry a
+    graph to that argument (_GarmentSkinFn: the same launches and bits forward, csrc/skin/skin_grad.hip backward); the neighbour lists are
+    constants of the graph, as knn_points(...).idx is in the reference, and so are the body, the pose, the regressors and the tables: any of them
+    requiring grad raises NotImplementedError.  The nearest-neighbour KNN is never differentiable.  With the flag off nothing here looks at
+    requires_grad and no output carries a graph."""
+    if tuning.current().garment_lbs_autograd and torch.is_grad_enabled():
+        for name, t in (("Tpose_vertices", Tpose_vertices), ("Tpose_root_joints", Tpose_root_joints), ("zeropose_vertices", zeropose_vertices),
+                        ("gt_pose", gt_pose), ("T_J_regressor", T_J_regressor), ("T_lbs_weights", T_lbs_weights),
+                        ("clip_J_regressor", clip_J_regressor), ("clip_lbs_weights", clip_lbs_weights)):
+            if t is not None and t.requires_grad:
+                raise NotImplementedError(f"lbs_garment_interpolation: {name} requires grad -- only pred_template_garment_v is differentiated (the "
+                                          "body, the pose and the skinning tables are constants of the graph)")
+        if pred_template_garment_v.requires_grad:
+            B, T = gt_pose.shape[0], gt_pose.shape[1]
+            posed, unposed, nn_d, nn_i = _GarmentSkinFn.apply(pred_template_garment_v, Tpose_vertices, Tpose_root_joints, zeropose_vertices, parents,
+                                                              gt_pose, T_J_regressor, T_lbs_weights, adj_old, K, clip_J_regressor, clip_lbs_weights)
+            stage1 = unposed.reshape(B, 1, -1, 3).repeat(1, T, 1, 1).reshape(B * T, -1, 3).contiguous()
+            return posed, KNN(dists=nn_d, idx=nn_i, knn=None), stage1.reshape(B, T, -1, 3)
+    return _interpolate(pred_template_garment_v, Tpose_vertices, Tpose_root_joints, zeropose_vertices, parents, gt_pose, T_J_regressor,
+                        T_lbs_weights, adj_old, K, clip_J_regressor, clip_lbs_weights)[:3]
+
+
+def _interpolate(pred_template_garment_v, Tpose_vertices, Tpose_root_joints, zeropose_vertices, parents, gt_pose, T_J_regressor, T_lbs_weights,
+                 adj_old, K, clip_J_regressor, clip_lbs_weights):
+    """The launches of lbs_garment_interpolation -> its three results and what the adjoint needs of them (see _GarmentSkinFn)."""
     assert pred_template_garment_v.dim() == 3 and pred_template_garment_v.shape[2] == 3
     assert gt_pose.dim() == 3 and gt_pose.shape[2] == 72
     B, T = gt_pose.shape[0], gt_pose.shape[1]
@@ -159,14 +204,55 @@ def lbs_garment_interpolation(pred_template_garment_v, Tpose_vertices, Tpose_roo
     else:
         Jf = L.vertices2jointsB(T_J_regressor.reshape(B * T, J, V).contiguous(), zero_v)
     _, A = L.batch_rigid_transform(gt_pose_mat, Jf, parents)
-    if shared_W:
-        nn_W = _blend(T_lbs_weights[:, 0].contiguous(), idx_k, d_k.contiguous(), 1)               # (B,Vg,J)
-    else:
-        nn_W = _blend(T_lbs_weights.reshape(B * T, V, J).contiguous(), idx_k, d_k.contiguous(), T)   # (B*T,Vg,J)  :374-382
+    d_k = d_k.contiguous()
+    Wt = T_lbs_weights[:, 0].contiguous() if shared_W else T_lbs_weights.reshape(B * T, V, J).contiguous()
+    nn_W = _blend(Wt, idx_k, d_k, 1 if shared_W else T)                            # (B,Vg,J) | (B*T,Vg,J)  :374-382
     if K > 1:
         nn_W = smooth_weights(nn_W, adj_old, 0.1, 100)                             # :385-390
     verts = L.skin(nn_W, A, inv_template_garment_v, group=T if shared_W else 1)   # :393, :406-408
-    return verts.reshape(B, T, -1, 3), nn1, inv_template_garment_v.reshape(B, T, -1, 3)
+    saved = (garment, body, idx_k, d_k, cW.contiguous(), inv_nn_W, inv_A, inv_garment, Wt, nn_W, A)
+    return verts.reshape(B, T, -1, 3), nn1, inv_template_garment_v.reshape(B, T, -1, 3), saved
+
+
+class _GarmentSkinFn(torch.autograd.Function):
+    """lbs_garment_interpolation as an autograd node, differentiable in the T-pose garment alone.  forward = _interpolate (the inference launches,
+    same bits) -> (posed (B,T,Vg,3), un-posed (B,Vg,3), and the K = 1 distances / indices, not differentiable).
+    Saved: g = x + root, the K neighbour lists and squared distances, both blended weight tensors (the un-posing's and the smoothed posing's),
+    inv_A, A, the un-posed garment u; the body and the tables are the caller's (contiguous copies only where the caller's were views).  Nothing
+    of the 100 smoothing steps is stored: the smoothing is linear.  At cfg4 (8 clips x 30 frames, Vg 4096, K 256, J 24): lists 2 x 33.6 MB,
+    weights 94.4 MB + 3.1 MB per-frame tables / 3.1 MB + 3.1 MB one table per clip, g, u, A, inv_A 1.2 MB: 165.8 MB / 74.6 MB.
+    backward (include/g4d_skin.h for the orders): skin adjoint over the clip's frames -> transposed smoothing -> blend adjoint (K) -> skin adjoint of
+    the un-posing -> blend adjoint (the min(64, K) prefix): four launches of csrc/skin/skin_grad.hip and one smoothing launch."""
+
+    @staticmethod
+    def forward(ctx, x, Tpose_vertices, Tpose_root_joints, zeropose_vertices, parents, gt_pose, T_J_regressor, T_lbs_weights, adj_old, K,
+                clip_J_regressor, clip_lbs_weights):
+        posed, nn1, _, saved = _interpolate(x, Tpose_vertices, Tpose_root_joints, zeropose_vertices, parents, gt_pose, T_J_regressor, T_lbs_weights,
+                                            adj_old, K, clip_J_regressor, clip_lbs_weights)
+        ctx.adj_old, ctx.K, ctx.T = adj_old, int(K), int(gt_pose.shape[1])
+        ctx.save_for_backward(*saved)
+        ctx.mark_non_differentiable(nn1.dists, nn1.idx)
+        return posed, saved[7], nn1.dists, nn1.idx
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_posed, d_unposed, _d_dists, _d_idx):
+        g, body, idx_k, d_k, cW, inv_nn_W, inv_A, u, Wt, nn_W, A = ctx.saved_tensors
+        B, Vg, K, T = g.shape[0], g.shape[1], ctx.K, ctx.T
+        shared = Wt.shape[0] == B and T > 1
+        du = None if d_unposed is None else d_unposed.float().contiguous()
+        dg = None
+        if d_posed is not None:
+            dy = d_posed.float().reshape(B * T, Vg, 3).contiguous()
+            du, d_nn_W = grad_ops.garment_skin_grad(B, T, nn_W, A, u, dy, d_add=du)
+            if K > 1:
+                d_nn_W = smooth_weights(d_nn_W, ctx.adj_old, 0.1, 100, transpose=True)
+            dg = grad_ops.knn_blend_grad(Wt, 1 if shared else T, idx_k, d_k, K, d_nn_W, g, body)
+        if du is None:
+            return (torch.zeros_like(g),) + (None,) * 11
+        dg, d_inv_W = grad_ops.garment_skin_grad(B, 1, inv_nn_W, inv_A, g, du, d_add=dg)
+        dg = grad_ops.knn_blend_grad(cW, 1, idx_k, d_k, min(64, K), d_inv_W, g, body, d_add=dg)
+        return (dg,) + (None,) * 11
 
 
 def _inv_template_pose_mats(F_, device):

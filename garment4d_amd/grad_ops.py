@@ -48,6 +48,34 @@ def mgn_skin_grad(clips, frames_per_clip, idx, W, inv_A, A, d_posed, d_stage1=No
     return out
 
 
+def garment_skin_grad(clips, frames_per_clip, W, A, verts, d_out, d_add=None, want_verts=True, want_W=True):
+    """The adjoint of lbs.skin() in the garment's form (g4d_garment_skin_grad_f32): W (clips * frames_per_clip, Vg, J) or (clips, Vg, J) = one table
+    per clip, A (frames, J, 4, 4), verts (clips, Vg, 3) shared by a clip's frames, d_out (frames, Vg, 3) -> (d_verts (clips, Vg, 3) = d_add + the
+    sum over the clip's frames, d_W in W's shape); either is None when not wanted."""
+    _lib.skin_lib()
+    Vg, J = W.shape[1], W.shape[2]
+    per_clip = int(W.shape[0] == clips and frames_per_clip > 1)
+    d_verts = torch.empty((clips, Vg, 3), dtype=torch.float32, device=W.device) if want_verts else None
+    d_W = torch.empty_like(W) if want_W else None
+    _lib.call("g4d_garment_skin_grad_f32", clips, frames_per_clip, Vg, J, W.data_ptr(), per_clip, A.data_ptr(), verts.data_ptr(), d_out.data_ptr(),
+              0 if d_add is None else d_add.data_ptr(), 0 if d_verts is None else d_verts.data_ptr(), 0 if d_W is None else d_W.data_ptr(),
+              _lib.stream_ptr())
+    return d_verts, d_W
+
+
+def knn_blend_grad(W, frames_per_clip, idx32, dists, k, d_blend, pts, ref, d_add=None):
+    """The adjoint of the inverse-distance blend carried on to the query points (g4d_knn_blend_grad_f32): W (F, V, J), idx32 / dists
+    (F / frames_per_clip, Vg, ldk) of which the first k entries of a row are used, d_blend (F, Vg, J), pts (clips, Vg, 3), ref (clips, V, 3)
+    -> d_pts (clips, Vg, 3) = d_add + d g."""
+    _lib.skin_lib()
+    F_, V, J = W.shape
+    clips, Vg, ldk = idx32.shape
+    out = torch.empty((clips, Vg, 3), dtype=torch.float32, device=W.device)
+    _lib.call("g4d_knn_blend_grad_f32", F_, frames_per_clip, Vg, V, int(k), ldk, J, W.data_ptr(), idx32.data_ptr(), dists.data_ptr(), d_blend.data_ptr(),
+              pts.data_ptr(), ref.data_ptr(), 0 if d_add is None else d_add.data_ptr(), out.data_ptr(), _lib.stream_ptr())
+    return out
+
+
 def linear_t(ds2d, weight):
     """dS . W for a Linear weight W (Cout, Cin): g4d_linear_f32 with W^T as the packed (Cin x Cout-deep) layer."""
     cin = weight.shape[1]

@@ -217,6 +217,18 @@ class PCALBSGarmentUseSegEncoderSeg(GarmentRefinementHead):
         return lbs_garment_interpolation(pred_template_garment_v, Tpose_vertices, Tpose_root_joints, zeropose_vertices, body_model.parents,
                                          gt_pose, T_J_regressor, T_lbs_weights, self.adj_old, K=K)
 
+    def skin_garment(self, tpose_garment, body_model, batch):
+        """The T-pose garment (nbatch, Vg, 3) or (nbatch, Vg * 3) posed by the batch's body: lbs_garment_interpolation with the batch's keys
+        (`Tpose_smpl_vertices_torch`, `Tpose_smpl_root_joints_torch`, `zeropose_smpl_vertices_torch`, `pose_torch`, `T_J_regressor`,
+        `T_lbs_weights`) and K = self.lbs_k -> (posed (nbatch,T,Vg,3), nearest-neighbour KNN, un-posed (nbatch,T,Vg,3)).  What _front calls;
+        under tuning.Tuning.garment_lbs_autograd it is differentiable in tpose_garment (garment_fit.py)."""
+        dev = tpose_garment.device
+        regressed = tpose_garment.reshape(tpose_garment.shape[0], -1, 3)
+        return self.lbs_garment_interpolation(
+            regressed, batch["Tpose_smpl_vertices_torch"].to(dev), batch["Tpose_smpl_root_joints_torch"].to(dev),
+            batch["zeropose_smpl_vertices_torch"].to(dev), body_model, batch["pose_torch"].to(dev), batch["T_J_regressor"].to(dev),
+            batch["T_lbs_weights"].to(dev), K=self.lbs_k)
+
     def forward(self, x, body_model, batch, *, group=None, clip_ids=None, precision="fp32"):
         """x (nbatch, T, N, 3); body_model needs `.parents`, `.faces`, `.J_regressor`; batch holds the reference's keys
         (`smpl_vertices_torch`, `Tpose_smpl_vertices_torch`, `Tpose_smpl_root_joints_torch`, `zeropose_smpl_vertices_torch`,
@@ -258,11 +270,7 @@ class PCALBSGarmentUseSegEncoderSeg(GarmentRefinementHead):
             self.vf_fid, self.vf_vid = self.vf_fid.to(dev), self.vf_vid.to(dev)
             self._body_faces = torch.from_numpy(np.asarray(body_model.faces).astype(np.int64)).to(dev)
         body_vn = mesh_utils.compute_vnorms(body_v, self._body_faces, self.vf_vid, self.vf_fid)
-        regressed = out["tpose_garment"].reshape(nbatch, -1, 3)
-        out["lbs_pred_garment_v"], out["lbs_nn"], out["lbs_stage1_pred_garment_v"] = self.lbs_garment_interpolation(
-            regressed, batch["Tpose_smpl_vertices_torch"].to(dev), batch["Tpose_smpl_root_joints_torch"].to(dev),
-            batch["zeropose_smpl_vertices_torch"].to(dev), body_model, batch["pose_torch"].to(dev), batch["T_J_regressor"].to(dev),
-            batch["T_lbs_weights"].to(dev), K=self.lbs_k)
+        out["lbs_pred_garment_v"], out["lbs_nn"], out["lbs_stage1_pred_garment_v"] = self.skin_garment(out["tpose_garment"], body_model, batch)
         cur = out["lbs_pred_garment_v"].reshape(nbatch * T, -1, 3).contiguous()
         return out, cur, body_v, body_vn, nbatch, T
 

@@ -102,6 +102,10 @@ class Tuning:
     lbs_autograd: bool = False         # lbs.py / body_models.py: lbs() of a grad-requiring betas or pose under grad returns (verts, posed joints) with a graph
                                        #  whose backward is the adjoint kernel of csrc/smpl/smpl_grad.hip (g4d_smpl_lbs_grad_f32), and SMPL / SMPLLayer.forward
                                        #  keep that graph (betas, body_pose, global_orient, transl); False: no graph, as it always was
+    garment_lbs_autograd: bool = False # garment_lbs.py: lbs_garment_interpolation of a grad-requiring T-pose garment under grad returns the posed and the un-posed
+                                       #  garment with a graph to that argument alone (the neighbour lists, the body, the pose and the tables are constants); the
+                                       #  backward is csrc/skin/skin_grad.hip (g4d_garment_skin_grad_f32, g4d_knn_blend_grad_f32) and the transposed smoothing;
+                                       #  False: no graph, as it always was
     # ---- lbs() routes (lbs.py).  NOT bit-identical to each other (different partitions of the blend sum; each within 1e-5 of the reference)
     lbs_fused: bool = True             # False: the five-step path that follows smplx/lbs.py line by line
     lbs_mfma: bool = True              # round 5: matrix-pipe route (g4d_lbs_mfma_f32), taken at every batch size
@@ -145,7 +149,7 @@ def from_environment() -> Tuning:
         fp_wide_table=_env_flag("G4D_FP_WIDE_TABLE", d.fp_wide_table), gcn_fuse_stack=_env_flag("G4D_GCN_FUSED", d.gcn_fuse_stack), gcn_autograd=_env_flag("G4D_GCN_AUTOGRAD", d.gcn_autograd),
         refine_autograd=_env_flag("G4D_REFINE_AUTOGRAD", d.refine_autograd), mgn_autograd=_env_flag("G4D_MGN_AUTOGRAD", d.mgn_autograd),
         stage1_autograd=_env_flag("G4D_STAGE1_AUTOGRAD", d.stage1_autograd), mlp_autograd=_env_flag("G4D_MLP_AUTOGRAD", d.mlp_autograd),
-        lbs_autograd=_env_flag("G4D_LBS_AUTOGRAD", d.lbs_autograd),
+        lbs_autograd=_env_flag("G4D_LBS_AUTOGRAD", d.lbs_autograd), garment_lbs_autograd=_env_flag("G4D_GARMENT_LBS_AUTOGRAD", d.garment_lbs_autograd),
         dropin_fused=_env_flag("G4D_DROPIN_FUSED", d.dropin_fused), dropin_whole_model=_env_flag("G4D_DROPIN_WHOLE", d.dropin_whole_model), lbs_mfma=_env_flag("G4D_LBS_MFMA", d.lbs_mfma), lbs_one_launch=_env_flag("G4D_LBS_ONE", d.lbs_one_launch),
         lbs_one_launch_max_b=_env_int("G4D_LBS_ONE_MAX_B", d.lbs_one_launch_max_b), nearest_cull=_env_flag("G4D_NEAREST_CULL", d.nearest_cull))
 
