@@ -13,7 +13,8 @@ lib/libg4d_render.so (render_lib(); record: tests/render_abi_snapshot.txt), and 
 lib/libg4d_scan.so (scan_lib(); record: tests/scan_abi_snapshot.txt), and the point-to-surface loss, include/g4d_fit.h + lib/libg4d_fit.so
 (fit_lib(); record: tests/fit_abi_snapshot.txt), and the adjoint of lbs(), include/g4d_smpl.h + lib/libg4d_smpl.so (smpl_lib(); record:
 tests/smpl_abi_snapshot.txt), and the adjoint of the garment skinning, include/g4d_skin.h + lib/libg4d_skin.so (skin_lib(); record:
-tests/skin_abi_snapshot.txt).  call() serves them too.  include/g4d_sets.h is a further header of
+tests/skin_abi_snapshot.txt), and the projective ray-depth loss, include/g4d_depth.h + lib/libg4d_depth.so (depth_lib(); record:
+tests/depth_abi_snapshot.txt).  call() serves them too.  include/g4d_sets.h is a further header of
 libg4d_hip.so ITSELF (sets_lib(); record: tests/sets_abi_snapshot.txt): entry points added after g4d.h's record was closed.
 """
 import ctypes
@@ -41,6 +42,9 @@ SMPL_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "g4d_smpl.h")
 # the sixth pair: the adjoint of the garment skinning (include/g4d_skin.h, libg4d_skin.so; skin_lib() loads it)
 SKIN_LIB_PATH = os.path.join(_HERE, "lib", "libg4d_skin.so")
 SKIN_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "g4d_skin.h")
+# the seventh pair: the projective ray-depth loss and its gradient (include/g4d_depth.h, libg4d_depth.so; depth_lib() loads it)
+DEPTH_LIB_PATH = os.path.join(_HERE, "lib", "libg4d_depth.so")
+DEPTH_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "g4d_depth.h")
 
 # a further header of libg4d_hip.so itself (no library of its own): entry points that came after the record of g4d.h (sets_lib() binds them)
 SETS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "g4d_sets.h")
@@ -210,6 +214,11 @@ def smpl_lib():
 def skin_lib():
     """libg4d_skin.so typed from include/g4d_skin.h: (CDLL, prototypes, constants)."""
     return load_pair(SKIN_HEADER_PATH, SKIN_LIB_PATH)
+
+
+def depth_lib():
+    """libg4d_depth.so typed from include/g4d_depth.h: (CDLL, prototypes, constants)."""
+    return load_pair(DEPTH_HEADER_PATH, DEPTH_LIB_PATH)
 
 
 def sets_lib():

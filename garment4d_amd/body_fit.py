@@ -3,11 +3,15 @@ evaluates (fit.point_mesh_distance: exact nearest-face search, truncated, weight
 pose and translation by the adjoint of lbs() (lbs.lbs_backward, csrc/smpl/smpl_grad.hip) -- the one input of the captured-data loop
 (render.py, scan.py, fit.py) that used to come from outside: `inputs['pose_torch']` and the betas of every frame.
 
+depth_body_fit_loss / fit_body_to_depth are the same fit for data that comes as depth images: the data term is depth_fit.depth_mesh_distance (the
+association comes from rasterizing the current body from the sensors' cameras; no nearest-face search), everything else is unchanged.
+
 Everything here needs tuning.Tuning.lbs_autograd for its gradients; the functions switch it on for their own calls of the body model and
 leave the caller's setting alone.  fp32 on the current torch stream, no atomics, no host round trip inside fit_body_to_scan's loop.  There is no
 fallback: without the libraries, or on CPU tensors, the calls raise."""
 import torch
 
+from . import depth_fit
 from . import fit
 from . import tuning
 
@@ -70,4 +74,35 @@ def fit_body_to_scan(body_model, points, weights, betas0, pose0, transl0, steps,
         opt.step()
     with torch.no_grad():
         losses[int(steps)] = body_fit_loss(body_model, betas, pose, transl, points, weights, trunc, pose_prior, shape_prior)["total"]
+    return betas.detach(), pose.detach(), transl.detach(), losses
+
+
+def depth_body_fit_loss(body_model, betas, pose, transl, depth_obs, cameras, weights=None, trunc=0.05, grazing=0.1, pose_prior=0.0, shape_prior=0.0):
+    """body_fit_loss for data that comes as depth images: depth_obs (K,B,h,w) of the K `cameras` (render.Camera), weights (K,B,h,w) >= 0 or None.
+    The data term is depth_fit.depth_mesh_distance(depth_obs, verts, body_model.faces, cameras, weights, trunc, grazing).loss -- the association
+    comes from rasterizing the current body, no nearest-face search --; the priors, the dict's keys and what total.backward() fills are
+    body_fit_loss's."""
+    verts = _body_vertices(body_model, betas, pose, transl)
+    f = depth_fit.depth_mesh_distance(depth_obs, verts, body_model.faces, cameras, weights, trunc, grazing)
+    pose_term = pose_prior * (pose[:, 3:] ** 2).mean() if pose.shape[1] > 3 else pose_prior * pose.sum() * 0
+    shape_term = shape_prior * (betas ** 2).mean()
+    return {"data": f.loss, "pose": pose_term, "shape": shape_term, "total": f.loss + pose_term + shape_term, "rms": f.rms, "inliers": f.inliers}
+
+
+def fit_body_to_depth(body_model, depth_obs, cameras, weights, betas0, pose0, transl0, steps, lr, trunc=0.05, grazing=0.1, pose_prior=0.0,
+                      shape_prior=0.0):
+    """fit_body_to_scan's plain Adam loop on depth_body_fit_loss(...)['total']: the body is rasterized anew at every step.  Returns (betas, pose,
+    transl, losses) as fit_body_to_scan does."""
+    betas, pose, transl = (t.detach().clone().requires_grad_(True) for t in (betas0, pose0, transl0))
+    opt = torch.optim.Adam([betas, pose, transl], lr=lr)
+    losses = torch.zeros(int(steps) + 1, dtype=torch.float32, device=depth_obs.device)
+    args = (depth_obs, cameras, weights, trunc, grazing, pose_prior, shape_prior)
+    for i in range(int(steps)):
+        opt.zero_grad(set_to_none=True)
+        total = depth_body_fit_loss(body_model, betas, pose, transl, *args)["total"]
+        total.backward()
+        losses[i] = total.detach()
+        opt.step()
+    with torch.no_grad():
+        losses[int(steps)] = depth_body_fit_loss(body_model, betas, pose, transl, *args)["total"]
     return betas.detach(), pose.detach(), transl.detach(), losses

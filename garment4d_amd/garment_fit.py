@@ -3,13 +3,20 @@
 skinning (garment_lbs.lbs_garment_interpolation's adjoint, csrc/skin/skin_grad.hip) to the T-pose garment and, through
 PCAGarmentEncoderSeg.PCA_inverse_transform, to the PCA coefficients -- the last piece of the captured-data loop scan.py -> body_fit.py -> here.
 
+depth_garment_fit_loss / fit_garment_to_depth are the same fit for data that comes as depth and label images: the data term is
+depth_fit.depth_mesh_distance on the body joined with the posed garment, so the body occludes the garment as it does for the sensor.
+
 Everything here needs tuning.Tuning.garment_lbs_autograd (and stage1_autograd for coefficients) for its gradients; the functions switch them on
 for their own calls of the model and leave the caller's setting alone.  The body (pose, T-pose vertices, tables: `batch`) is a constant: joint
 body + garment fitting is out of scope.  fp32 on the current torch stream, no atomics, no host round trip inside fit_garment_to_scan's loop.
 There is no fallback: without the libraries, or on CPU tensors, the calls raise."""
+import numpy as np
 import torch
 
+from . import _cache
+from . import depth_fit
 from . import fit
+from . import render
 from . import tuning
 
 
@@ -77,4 +84,60 @@ def fit_garment_to_scan(model, body_model, batch, coeff_or_verts0, points, weigh
         opt.step()
     with torch.no_grad():
         losses[int(steps)] = garment_fit_loss(model, body_model, batch, x, points, weights, garment_faces, trunc, coeff_prior)["total"]
+    return x.detach(), losses
+
+
+_label_cache = {}
+
+
+def _joined_face_labels(faces, nfb, garment_label, device):
+    """The labelling of scan.scan_batch for the joined mesh: body faces 0, garment faces `garment_label`; (nf) int32 on `device`, once per mesh."""
+    def build():
+        assert not torch.cuda.is_current_stream_capturing(), "garment_fit: build the face labels before the capture (call once eagerly)"
+        host = np.zeros(len(faces), np.int32)
+        host[nfb:] = int(garment_label)
+        return torch.from_numpy(host).to(device)
+    return _cache.by_identity(_label_cache, 8, (faces,), (int(nfb), int(garment_label), str(device)), build)
+
+
+def depth_garment_fit_loss(model, body_model, batch, coeff_or_verts, depth_obs, labels_obs, cameras, garment_faces, garment_label, weights=None, trunc=0.05,
+                           grazing=0.1, coeff_prior=0.0):
+    """garment_fit_loss for data that comes as depth images: depth_obs (K,nbatch*T,h,w) and labels_obs (K,nbatch*T,h,w) int32 of the K `cameras`
+    (what depth_fit.sensor_depth gives with scan.scan_batch's labelling: body 0, garment `garment_label`, background -1), weights or None.
+    The mesh is the body batch['smpl_vertices_torch'] (nbatch,T,Vb,3) -- a constant -- joined with the posed garment + root joint
+    (render._joined_faces), so the body occludes the garment as it does for the sensor, and a garment ray pairs only with a garment face.
+    data = depth_fit.depth_mesh_distance(...).loss over the rays of BOTH labels (the body's rays carry no gradient: its vertices are constants;
+    pass weights = (labels_obs == garment_label) to leave them out of W); the gradient reaches the garment vertices through the torch.cat and goes
+    on through the skinning adjoint.  prior, total, rms, inliers, posed: garment_fit_loss's."""
+    _, posed = _posed_garment(model, body_model, batch, coeff_or_verts)
+    nbatch, T, Vg = posed.shape[:3]
+    body = batch["smpl_vertices_torch"].to(posed.device)
+    if not (body.dim() == 4 and tuple(body.shape[:2]) == (nbatch, T) and body.shape[-1] == 3):
+        raise ValueError("depth_garment_fit_loss: batch['smpl_vertices_torch'] must be (nbatch, T, Vb, 3)")
+    Vb = int(body.shape[2])
+    root = batch["smpl_root_joints_torch"].to(posed.device).reshape(nbatch * T, 1, 3)
+    verts = torch.cat([body.reshape(nbatch * T, Vb, 3).detach(), posed.reshape(nbatch * T, Vg, 3) + root], 1)
+    faces = render._joined_faces(body_model.faces, garment_faces, Vb)
+    face_labels = _joined_face_labels(faces, int(np.asarray(body_model.faces).shape[0]), garment_label, posed.device)
+    f = depth_fit.depth_mesh_distance(depth_obs, verts, faces, cameras, weights, trunc, grazing, labels_obs, face_labels)
+    prior = coeff_prior * (coeff_or_verts ** 2).mean() if coeff_or_verts.dim() == 2 else f.loss * 0
+    return {"data": f.loss, "prior": prior, "total": f.loss + prior, "rms": f.rms, "inliers": f.inliers, "posed": posed}
+
+
+def fit_garment_to_depth(model, body_model, batch, coeff_or_verts0, depth_obs, labels_obs, cameras, garment_faces, garment_label, steps, lr, weights=None,
+                         trunc=0.05, grazing=0.1, coeff_prior=0.0):
+    """fit_garment_to_scan's plain Adam loop on depth_garment_fit_loss(...)['total']: the joined mesh is rasterized anew at every step.  Returns
+    (fitted tensor (detached), losses) as fit_garment_to_scan does."""
+    x = coeff_or_verts0.detach().clone().requires_grad_(True)
+    opt = torch.optim.Adam([x], lr=lr)
+    losses = torch.zeros(int(steps) + 1, dtype=torch.float32, device=depth_obs.device)
+    args = (depth_obs, labels_obs, cameras, garment_faces, garment_label, weights, trunc, grazing, coeff_prior)
+    for i in range(int(steps)):
+        opt.zero_grad(set_to_none=True)
+        total = depth_garment_fit_loss(model, body_model, batch, x, *args)["total"]
+        total.backward()
+        losses[i] = total.detach()
+        opt.step()
+    with torch.no_grad():
+        losses[int(steps)] = depth_garment_fit_loss(model, body_model, batch, x, *args)["total"]
     return x.detach(), losses
