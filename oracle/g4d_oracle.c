@@ -21,14 +21,22 @@
  *   2           fmaf(dz,dz, fmaf(dy,dy, dx*dx))  the other pairing / the accumulate-loop shape of chamferdist's knn.
  * This file is built with -ffp-contract=off, so the only fused operations are the explicit fmaf() calls.
  *
- * PARITY PINNING: the reference's native kernels are CUDA-only and cannot be built or run in
- * this environment (no nvcc, no NVIDIA GPU; they need the CUDA runtime headers), and the
- * reference ships no tests or golden vectors for them.  The kernel-level restatement is
- * therefore "parity unpinned" against real CUDA bits -- the FPS / ball-query / three_nn index
- * goldens in tests/golden/ops*.npz are THIS file's output routed through the reference's Python
- * wrappers, i.e. a regression pin, not an independent one; what IS pinned (tests/golden/) is the
- * reference's own Python layer (pointnet2_utils / pointnet2_modules / lbs / GraphConvolution)
- * executed in the build container on top of these kernels.
+ * PARITY PINNING: the reference ships no tests or golden vectors for its native kernels, but its four kernel files hold
+ * nothing CUDA-specific, and `make -C oracle ref` compiles them AS THEY ARE for gfx950 (hipcc -O2 -ffp-contract=off, four
+ * shadow headers of our own under ref_shim/, C entry points in ref_entry.hip) into _ref/libpointnet2_ref.so.
+ *   PINNED: the reference's own kernel source, executed on an MI355X, against this file in mode 0 (`off`) and against the
+ *   product in mode `off`, bit for bit, for all nine ops -- tests/test_ref_kernels_gpu.py (live, where _ref/ was built) and
+ *   tests/golden/ops_ref_hip_off.npz (its recorded outputs; tests/test_ref_kernels_cpu.py holds this file to them on any
+ *   machine): the block-size-dependent tie-break of the FPS tree, opt_n_threads() for every n up to 40000, the temp in/out
+ *   contract, the ball query's fill-with-the-first-hit and cnt handling, the strict `<` cascade and 1e40 sentinels of
+ *   three_nn, NaN / inf coordinates, the three scatter-add backwards on exactly summable inputs.  No case disagreed.
+ *   NOT PINNED: which multiply-adds `nvcc -O2` fuses in the squared distance -- mode 1 stays an assumption until somebody
+ *   supplies tests/golden/ops_cuda.npz (tests/test_cuda_pin.py).  hipcc's own default contraction of that expression (two
+ *   rounded products, one fma, one rounded add) is NONE of the three modes, which is why the reference build must be, and
+ *   is, compiled with -ffp-contract=off and held to mode 0 only.
+ * The index goldens in tests/golden/ops*.npz remain THIS file's output routed through the reference's Python wrappers (a
+ * regression pin); the reference's own Python layer (pointnet2_utils / pointnet2_modules / lbs / GraphConvolution) executed on
+ * top of these kernels is pinned by the rest of tests/golden/.
  */
 #include <math.h>
 #include <stdint.h>

@@ -9,7 +9,7 @@ What is imported from the reference, unmodified:
   * modules/pointnet2/pointnet2/{pointnet2_utils,pointnet2_modules,pytorch_utils}.py, with the C
     oracle injected as the extension module `pointnet2_cuda` and the legacy
     torch.cuda.{Int,Float}Tensor constructors mapped to CPU tensors (the reference's native
-    kernels are CUDA-only and cannot be built here -- see oracle/g4d_oracle.c header);
+    kernels need a GPU; this generator runs without one -- see oracle/g4d_oracle.c header);
   * smplx/smplx/lbs.py (lbs, batch_rigid_transform, batch_rodrigues, vertices2jointsB);
   * modules/pygcn/{layers,utils}.py (GraphConvolution, normalize).
 """

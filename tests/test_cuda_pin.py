@@ -1,6 +1,8 @@
 """Pin against the reference's REAL CUDA extension, when somebody supplies its outputs (scripts/dump_reference_indices.py ->
 tests/golden/ops_cuda.npz; INTEGRATION.md "Pinning the index kernels").  Without the file the pin tests skip: the kernel-level
-restatement in oracle/g4d_oracle.c is then pinned against the reference's Python layers only."""
+restatement in oracle/g4d_oracle.c is then pinned against the reference's Python layers and, in `off` mode, against the reference's
+own kernel source compiled for gfx950 (tests/test_ref_kernels_{gpu,cpu}.py) -- nvcc's contraction choice stays an assumption
+(DESIGN.md section 3)."""
 import os
 import subprocess
 import sys
@@ -61,7 +63,7 @@ def test_dump_script_round_trips_through_a_stand_in_extension(tmp_path, golden_o
 
 
 @pytest.mark.skipif(not os.path.exists(PIN), reason="tests/golden/ops_cuda.npz not supplied (run scripts/dump_reference_indices.py on a machine "
-                                                    "with the reference's CUDA extension): index kernels pinned against the reference's Python only")
+                                                    "with the reference's CUDA extension): nvcc's contraction choice stays an assumption")
 def test_oracle_matches_the_real_cuda_extension(golden_ops):
     pin = np.load(PIN)
     modes = _matching_modes(pin, golden_ops)
