@@ -15,8 +15,10 @@ lib/libg4d_scan.so (scan_lib(); record: tests/scan_abi_snapshot.txt), and the po
 tests/smpl_abi_snapshot.txt), and the adjoint of the garment skinning, include/g4d_skin.h + lib/libg4d_skin.so (skin_lib(); record:
 tests/skin_abi_snapshot.txt), and the projective ray-depth loss, include/g4d_depth.h + lib/libg4d_depth.so (depth_lib(); record:
 tests/depth_abi_snapshot.txt).  call() serves them too.  include/g4d_sets.h is a further header of
-libg4d_hip.so ITSELF (sets_lib(); record: tests/sets_abi_snapshot.txt): entry points added after g4d.h's record was closed.
+libg4d_hip.so ITSELF (sets_lib(); record: tests/sets_abi_snapshot.txt): entry points added after g4d.h's record was closed; include/g4d_live.h
+is another (live_lib(); record: tests/live_abi_snapshot.txt): the live-cloud scope, opened from Python with live_scope().
 """
+import contextlib
 import ctypes
 import os
 import re
@@ -48,10 +50,12 @@ DEPTH_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "g4d_depth.h
 
 # a further header of libg4d_hip.so itself (no library of its own): entry points that came after the record of g4d.h (sets_lib() binds them)
 SETS_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "g4d_sets.h")
+# ... and the live-cloud scope of the same library (live_lib() binds it, live_scope() opens one)
+LIVE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "g4d_live.h")
 
 _lib = None
 _header = None   # HEADER_PATH once the names below are bound from it
-_more = {}       # library path -> (its CDLL, {entry point: (restype, argtypes)}, its G4D_* constants) of every further pair load_pair() loaded
+_more = {}       # (header path, library path) -> (its CDLL, {entry point: (restype, argtypes)}, its G4D_* constants) of every further pair load_pair() loaded
 
 
 class G4DError(RuntimeError):
@@ -172,7 +176,8 @@ def lib():
 def load_pair(header_path, lib_path):
     """Load a further library once, typed as its own header declares it (the same parse as include/g4d.h's): call() then finds its entry
     points.  libg4d_hip.so is loaded first -- such a library links against it and shares its error state.  Returns (CDLL, prototypes, constants)."""
-    if lib_path not in _more:
+    key = (header_path, lib_path)   # (libg4d_hip.so itself is the library of more than one further header)
+    if key not in _more:
         lib()
         if not os.path.exists(lib_path):
             raise G4DError(f"{lib_path} not found: the HIP extension is not built. Run `python -c 'import __graft_entry__ as g; g.build()'` "
@@ -187,8 +192,8 @@ def load_pair(header_path, lib_path):
             fn = getattr(L, name)  # AttributeError if the library does not export a declared symbol
             fn.argtypes = argtypes
             fn.restype = restype
-        _more[lib_path] = (L, protos, consts)
-    return _more[lib_path]
+        _more[key] = (L, protos, consts)
+    return _more[key]
 
 
 def render_lib():
@@ -226,6 +231,25 @@ def sets_lib():
     return load_pair(SETS_HEADER_PATH, LIB_PATH)
 
 
+def live_lib():
+    """libg4d_hip.so's entry points of include/g4d_live.h, typed from that header: (CDLL, prototypes, constants)."""
+    return load_pair(LIVE_HEADER_PATH, LIB_PATH)
+
+
+@contextlib.contextmanager
+def live_scope(count, capacity):
+    """Launches made (or captured) by this thread inside the block honour a live-cloud count read on the device (include/g4d_live.h): `count`
+    is a one-element int32 HIP tensor -- kept alive, and rewritten on the launching stream, by the caller -- and `capacity` the number of clouds
+    the calls inside are launched with.  Scopes do not nest."""
+    live_lib()
+    assert count.is_cuda and count.numel() == 1 and str(count.dtype) == "torch.int32"
+    call("g4d_live_scope_begin", count.data_ptr(), int(capacity))
+    try:
+        yield
+    finally:
+        call("g4d_live_scope_end")
+
+
 def _entry(name):
     """The loaded function behind an entry point's name: libg4d_hip.so's, or that of whichever further loaded library declares it."""
     L = lib()
@@ -238,7 +262,7 @@ def _entry(name):
 
 _TRACE = os.environ.get("G4D_TRACE_CALLS", "0") != "0"   # debugging: every C-ABI call with its integer / float arguments on stderr
 _TIMED = None   # measurement: a list collecting (name, integer args, start event, end event) of every call (timed_calls)
-_UNTIMED = ("g4d_tuning_set", "g4d_tuning_set_thread", "g4d_launch_group_begin")   # host state only: nothing to put events around
+_UNTIMED = ("g4d_tuning_set", "g4d_tuning_set_thread", "g4d_launch_group_begin", "g4d_live_scope_begin", "g4d_live_scope_end")   # host state only: nothing to put events around
 
 
 class timed_calls:

@@ -117,6 +117,41 @@ extern "C" int g4d_tuning_set_thread(const char *key, long long value, int set) 
     return G4D_EINVAL;
 }
 
+// ---- live-cloud scope (include/g4d_live.h): per host thread, like the tuning overrides -- launchers ask on the thread that launches / captures
+#include "../../include/g4d_live.h"
+namespace g4d {
+static thread_local const int *t_live_count = nullptr;
+static thread_local int t_live_cap = 0;
+LiveRows live_for_clouds(long long b, long long rows_per_cloud) {
+    if (!t_live_count || b != t_live_cap || rows_per_cloud <= 0 || rows_per_cloud * b >= (1ll << 31)) return {nullptr, 0, 0};
+    return {t_live_count, t_live_cap, (int)rows_per_cloud};
+}
+LiveRows live_for_rows(long long rows) {
+    if (!t_live_count || rows <= 0 || rows % t_live_cap != 0) return {nullptr, 0, 0};
+    return live_for_clouds(t_live_cap, rows / t_live_cap);
+}
+}  // namespace g4d
+
+extern "C" int g4d_live_scope_begin(const int *live_clouds_dev, int capacity_clouds) {
+    G4D_REQUIRE(live_clouds_dev && capacity_clouds >= 1, "g4d_live_scope_begin: needs a device pointer and a capacity >= 1");
+    G4D_REQUIRE(!g4d::t_live_count, "g4d_live_scope_begin: a scope of %d clouds is already open on this thread (scopes do not nest)", g4d::t_live_cap);
+    g4d::t_live_count = live_clouds_dev;
+    g4d::t_live_cap = capacity_clouds;
+    return G4D_OK;
+}
+extern "C" int g4d_live_scope_end(void) {
+    G4D_REQUIRE(g4d::t_live_count, "g4d_live_scope_end: no scope is open on this thread");
+    g4d::t_live_count = nullptr;
+    g4d::t_live_cap = 0;
+    return G4D_OK;
+}
+extern "C" int g4d_live_scope_capacity(void) { return g4d::t_live_count ? g4d::t_live_cap : 0; }
+extern "C" long long g4d_live_scope_rows_per_cloud(long long clouds, long long rows) {
+    if (clouds == 0) return 0;
+    const g4d::LiveRows l = clouds < 0 ? g4d::live_for_rows(rows) : (rows % clouds == 0 ? g4d::live_for_clouds(clouds, rows / clouds) : g4d::LiveRows{nullptr, 0, 0});
+    return l.count ? l.per_cloud : 0;
+}
+
 extern "C" int g4d_version(void) { return 263; /* 263: g4d_pos_encode_grad_f32, g4d_temporal_attention_grad_f32 (+ size queries) added, none changed; 262: g4d_spmm_rows_grad_f32, g4d_col_sum_rows_f32, g4d_gemm_tn_f32 (+ size queries) added, none changed; 261: g4d_mgn_skin_f32 added, none changed; 260 = round 6: g4d_mlp_run / g4d_mlp_args, g4d_mlp_chain_group_table_ws_f32 + g4d_sa_table_ws_bytes / _supported (include/g4d.h); 206: round 2 */ }
 extern "C" const char *g4d_last_error(void) { return g4d::g_err; }
 

@@ -58,8 +58,9 @@ __device__ __forceinline__ int query_cell(float v, float lo, float inv_c, int g)
 template <int NS, int FM, bool SET>
 __global__ void __launch_bounds__(256) ball_grid_query_kernel(int n, int m, int qpw, const BgArgs a, const float *__restrict__ new_xyz_all,
                                                              const float *__restrict__ xyz_all, const unsigned char *__restrict__ ws_all,
-                                                             size_t ws_stride, int cmax) {
+                                                             size_t ws_stride, int cmax, const LiveRows live) {
     __shared__ int lst[4][NS][kCap];
+    if ((int)blockIdx.y >= live_clouds(live, (int)gridDim.y)) return;   // a dead cloud of a live-cloud scope: before the first load
     const int t = threadIdx.x, lane = t & 63;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int b = blockIdx.y;
@@ -358,8 +359,9 @@ size_t grid_records_offset(int n) { return kGridHdrBytes + ((((size_t)grid_cmax(
 template <int NS, int FM, bool SET>
 static void grid_query_launch(dim3 grid, hipStream_t st, int n, int m, int qpw, const BgArgs &a, const float *new_xyz, const float *xyz,
                               const void *ws) {
+    const LiveRows live = live_for_clouds(grid.y, m);
     hipLaunchKernelGGL((ball_grid_query_kernel<NS, FM, SET>), grid, dim3(256), 0, st, n, m, qpw, a, new_xyz, xyz,
-                       reinterpret_cast<const unsigned char *>(ws), grid_cloud_bytes(n), grid_cmax(n));
+                       reinterpret_cast<const unsigned char *>(ws), grid_cloud_bytes(n), grid_cmax(n), live);
 }
 
 template <bool SET>

@@ -201,7 +201,8 @@ __global__ void __launch_bounds__(256) ball_query_multi_kernel(const BqMulti q) 
 // QW queries per wave: 1 for a lone B = 8 step (more, smaller workgroups: latency), 4 for a coalesced call (a workgroup's LDS staging of
 // the cloud and its fixed costs are shared by 16 queries instead of 4; the per-query arithmetic is the same: identical outputs).
 template <int NS, int FM, int QW>
-__global__ void __launch_bounds__(256) search_multi_kernel(const BqMulti q, const NNMulti nq, int bq_blocks) {
+__global__ void __launch_bounds__(256) search_multi_kernel(const BqMulti q, const NNMulti nq, int bq_blocks, const LiveRows live) {
+    if ((int)blockIdx.y >= live_clouds(live, (int)gridDim.y)) return;   // a dead cloud of a live-cloud scope: before the first load and barrier
     if ((int)blockIdx.x < bq_blocks) {
         if ((int)blockIdx.x < q.blk0) ball_query_body<QW, NS, FM>(q.n[0], q.m[0], q.a[0], q.new_xyz[0], q.xyz[0], blockIdx.x, blockIdx.y);
         else ball_query_body<QW, NS, FM>(q.n[1], q.m[1], q.a[1], q.new_xyz[1], q.xyz[1], (int)blockIdx.x - q.blk0, blockIdx.y);
@@ -665,9 +666,10 @@ extern "C" int g4d_search_multi_f32(int b, int nscales, int n0, int m0, const fl
     const int bq_blocks = q.blk0 + (m1 + 4 * qw - 1) / (4 * qw);
     dim3 grid((unsigned)(bq_blocks + nblocks), (unsigned)b);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const LiveRows live = live_for_clouds(b, 1);   // (whole clouds only: the kernel asks for the live clouds, never for rows)
 #define G4D_SM(NSV)                                                                                                                                          \
-    if (qw == 4) { G4D_WITH_FM(distance_contraction(), hipLaunchKernelGGL((search_multi_kernel<NSV, FM, 4>), grid, dim3(256), 0, st, q, nq, bq_blocks)) }   \
-    else { G4D_WITH_FM(distance_contraction(), hipLaunchKernelGGL((search_multi_kernel<NSV, FM, 1>), grid, dim3(256), 0, st, q, nq, bq_blocks)) }
+    if (qw == 4) { G4D_WITH_FM(distance_contraction(), hipLaunchKernelGGL((search_multi_kernel<NSV, FM, 4>), grid, dim3(256), 0, st, q, nq, bq_blocks, live)) }   \
+    else { G4D_WITH_FM(distance_contraction(), hipLaunchKernelGGL((search_multi_kernel<NSV, FM, 1>), grid, dim3(256), 0, st, q, nq, bq_blocks, live)) }
     switch (nscales) {
         case 1: G4D_SM(1) break;
         case 2: G4D_SM(2) break;

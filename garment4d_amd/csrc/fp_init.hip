@@ -42,6 +42,7 @@ struct FpInitArgs {
     int relu1, relu2, relu3;
     float *out; int ldo;                  // last layer (rows, 128)
     float *tap; int tap_ld;               // output of the 256 -> 128 layer (rows, 128); may be NULL
+    LiveRows live;                        // live-cloud scope of the launch (count == nullptr: none)
 };
 
 namespace {
@@ -63,15 +64,18 @@ __global__ void __launch_bounds__(256, 2) fp_init_kernel(const FpInitArgs a) {
     float (*s_stage)[STAGE] = reinterpret_cast<float (*)[STAGE]>(fp_init_smem);
     __shared__ __attribute__((aligned(16))) float s_sc1[C1], s_sh1[C1], s_sc2[C2], s_sh2[C2], s_sc3[C3], s_sh3[C3];
     const int tid = threadIdx.x;
+    // under a live-cloud scope: the live clouds' rows.  Read once, here; the four waves of a workgroup derive the SAME tile count from it (the
+    // count does not change while a launch runs), which is what the barriers inside the loop need
+    const int rows = live_rows(a.live, a.rows);
+    const int ntile = (rows + 15) >> 4;
+    if ((int)blockIdx.x * 4 >= ntile) return;        // no tile for this workgroup: it leaves before its first load and barrier
     s_sc1[tid] = a.sc1[tid]; s_sh1[tid] = a.sh1[tid];
     if (tid < C2) { s_sc2[tid] = a.sc2[tid]; s_sh2[tid] = a.sh2[tid]; s_sc3[tid] = a.sc3[tid]; s_sh3[tid] = a.sh3[tid]; }
     __syncthreads();
 
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // (uniform: the copy destinations below go through M0)
     const int fi = lane & 15, fq = lane >> 4;
-    const int ntile = (a.rows + 15) >> 4;
     const int nwaves = gridDim.x * 4, wg = blockIdx.x * 4 + wave;
-    if ((int)blockIdx.x * 4 >= ntile) return;
     const int iters = (ntile - (int)blockIdx.x * 4 + nwaves - 1) / nwaves;   // the same for the four waves (barriers inside the loop)
     auto tile_of = [&](int it) { return min(wg + it * nwaves, ntile - 1); };
     auto live = [&](int it) { return wg + it * nwaves < ntile; };
@@ -153,7 +157,7 @@ __global__ void __launch_bounds__(256, 2) fp_init_kernel(const FpInitArgs a) {
     struct Raw { int i0, i1, i2; float d0, d1, d2; };
     auto load_raw = [&](int tile) {
         Raw r;
-        const int row = min(tile * 16 + fi, a.rows - 1);
+        const int row = min(tile * 16 + fi, rows - 1);
         const int *ix = a.nn_idx + (size_t)row * 3;
         const float *dd = a.dist2 + (size_t)row * 3;
         r.i0 = ix[0]; r.i1 = ix[1]; r.i2 = ix[2]; r.d0 = dd[0]; r.d1 = dd[1]; r.d2 = dd[2];
@@ -164,7 +168,7 @@ __global__ void __launch_bounds__(256, 2) fp_init_kernel(const FpInitArgs a) {
         Ctx c;
         const InterpW w = interp_weights(r.d0, r.d1, r.d2);
         c.w0 = w.w0; c.w1 = w.w1; c.w2 = w.w2;
-        const int row = min(tile * 16 + fi, a.rows - 1);
+        const int row = min(tile * 16 + fi, rows - 1);
         const int b0 = __builtin_amdgcn_readfirstlane((tile * 16) / a.n);   // a tile touches at most two clouds (n >= 16)
         const unsigned base = (unsigned)(b0 + (row >= (b0 + 1) * a.n ? 1 : 0)) * (unsigned)a.m;
         c.k0 = (base + (unsigned)r.i0) * (unsigned)a.tab_ld + fq * 4; c.k1 = (base + (unsigned)r.i1) * (unsigned)a.tab_ld + fq * 4;
@@ -174,7 +178,7 @@ __global__ void __launch_bounds__(256, 2) fp_init_kernel(const FpInitArgs a) {
     struct Skip { f32x4 s[K0]; };
     auto load_skip = [&](int tile) {
         Skip k;
-        const float *p = a.skip + (size_t)min(tile * 16 + fi, a.rows - 1) * C0 + fq * 4;
+        const float *p = a.skip + (size_t)min(tile * 16 + fi, rows - 1) * C0 + fq * 4;
 #pragma unroll
         for (int ks = 0; ks < K0; ++ks) k.s[ks] = *reinterpret_cast<const f32x4u *>(p + ks * 16);
         return k;
@@ -220,7 +224,7 @@ __global__ void __launch_bounds__(256, 2) fp_init_kernel(const FpInitArgs a) {
         G4D_FSTAMP(3)   // tile epilogue (last layer's stores) + loop
         const int tile = tile_of(it);
         par0 = it & 1;
-        const bool row_ok = tile * 16 + fi < a.rows && live(it);
+        const bool row_ok = tile * 16 + fi < rows && live(it);
         // ---- layer 1: the skip columns on the matrix pipe, transposed (A = weights, B = the skip row's 16 columns of the k-step)
         f32x4 sring[2];
 #pragma unroll
@@ -280,7 +284,7 @@ __global__ void __launch_bounds__(256, 2) fp_init_kernel(const FpInitArgs a) {
                 for (int e = 0; e < 4; ++e) h2[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[e], h1[ks][e], h2[ct], 0, 0, 0);
             }
         }
-        const size_t orow = (size_t)min(tile * 16 + fi, a.rows - 1);
+        const size_t orow = (size_t)min(tile * 16 + fi, rows - 1);
 #pragma unroll
         for (int ct = 0; ct < T2; ++ct) {
             if ((ct & 3) == 0) __builtin_amdgcn_sched_barrier(0);
@@ -363,7 +367,7 @@ int g4d::fp_init_try(const StackCall &c, hipStream_t st) {
     G4D_REQUIRE(in.ldo >= c.Cout[2] && (!c.tap_out || c.tap_ld >= c.Cout[1]) && in.tab_ld % 4 == 0, "g4d_mlp_chain_interp_init_f32: output row stride %d < %d channels, tap stride %d < %d or table stride %d not a multiple of 4",
                 in.ldo, c.Cout[2], c.tap_ld, c.Cout[1], in.tab_ld);
     FpInitArgs a;
-    a.rows = (int)c.rows; a.n = in.n; a.m = in.m; a.skip = in.skip; a.tab = in.tab; a.tab_ld = in.tab_ld; a.dist2 = in.dist2; a.nn_idx = in.nn_idx;
+    a.rows = (int)c.rows; a.live = live_for_clouds(c.rows / in.n, in.n); a.n = in.n; a.m = in.m; a.skip = in.skip; a.tab = in.tab; a.tab_ld = in.tab_ld; a.dist2 = in.dist2; a.nn_idx = in.nn_idx;
     a.W1 = W[0]; a.sc1 = c.scale[0]; a.sh1 = c.shift[0]; a.W2 = W[1]; a.sc2 = c.scale[1]; a.sh2 = c.shift[1]; a.W3 = W[2]; a.sc3 = c.scale[2]; a.sh3 = c.shift[2];
     a.relu1 = c.relu[0]; a.relu2 = c.relu[1]; a.relu3 = c.relu[2];
     a.out = in.out; a.ldo = in.ldo; a.tap = c.tap_out; a.tap_ld = c.tap_ld;

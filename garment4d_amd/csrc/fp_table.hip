@@ -34,6 +34,7 @@ struct FpTabArgs {
     int cout4, relu4;                     // valid channels of the last layer (<= 16)
     float *out;  int ldo;                 // (rows, cout4) logits
     float *tap;  int tap_ld;              // (rows, 64) output of the 128 -> 64 layer
+    LiveRows live;                        // live-cloud scope of the launch (count == nullptr: none)
 };
 
 constexpr int kC1 = 128, kC2 = 64, kC3 = 32, kC4 = 16;
@@ -51,6 +52,9 @@ __global__ void __launch_bounds__(256, kD <= 4 ? 3 : 2) fp_table_head_kernel(con
     __shared__ __attribute__((aligned(16))) float s_w2[NW2], s_w3[NW3], s_w4[NW4];
     __shared__ __attribute__((aligned(16))) float s_ps[kC1], s_pf[kC1], s_sc2[kC2], s_sh2[kC2], s_sc3[kC3], s_sh3[kC3], s_sc4[kC4], s_sh4[kC4];
     const int tid = threadIdx.x;
+    const int rows = live_rows(a.live, a.rows);      // under a live-cloud scope: the live clouds' rows
+    const int ntile = (rows + 15) >> 4;
+    if ((int)blockIdx.x * 4 >= ntile) return;        // no tile for this workgroup: it leaves before the 42 KB weight load
     for (int i = tid; i < NW2 / 4; i += 256) reinterpret_cast<f32x4 *>(s_w2)[i] = reinterpret_cast<const f32x4 *>(a.W2)[i];
     if constexpr (HEAD) {
         for (int i = tid; i < NW3 / 4; i += 256) reinterpret_cast<f32x4 *>(s_w3)[i] = reinterpret_cast<const f32x4 *>(a.W3)[i];
@@ -66,7 +70,6 @@ __global__ void __launch_bounds__(256, kD <= 4 ? 3 : 2) fp_table_head_kernel(con
 
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // (uniform: tile numbers, cloud numbers and their divisions run on the scalar unit)
     const int fi = lane & 15, fq = lane >> 4;
-    const int ntile = (a.rows + 15) >> 4;
     const int nwaves = gridDim.x * 4, wg = blockIdx.x * 4 + wave;
     if (wg >= ntile) return;
     const int iters = (ntile - wg + nwaves - 1) / nwaves;
@@ -76,7 +79,7 @@ __global__ void __launch_bounds__(256, kD <= 4 ? 3 : 2) fp_table_head_kernel(con
     struct Raw { int i0, i1, i2; float d0, d1, d2; int orow; };
     auto load_raw = [&](int tile) {
         Raw r;
-        const int row = min(tile * 16 + fi, a.rows - 1);
+        const int row = min(tile * 16 + fi, rows - 1);
         const int *ix = a.nn_idx + (size_t)row * 3;
         const float *dd = a.dist2 + (size_t)row * 3;
         r.i0 = ix[0]; r.i1 = ix[1]; r.i2 = ix[2];
@@ -93,7 +96,7 @@ __global__ void __launch_bounds__(256, kD <= 4 ? 3 : 2) fp_table_head_kernel(con
         Ctx c;
         const InterpW w = interp_weights(r.d0, r.d1, r.d2);
         c.w0 = w.w0; c.w1 = w.w1; c.w2 = w.w2;
-        const int row = min(tile * 16 + fi, a.rows - 1);
+        const int row = min(tile * 16 + fi, rows - 1);
         const int b0 = __builtin_amdgcn_readfirstlane((tile * 16) / a.n);
         const unsigned base = (unsigned)(b0 + (row >= (b0 + 1) * a.n ? 1 : 0)) * (unsigned)a.m;
         c.k0 = (base + (unsigned)r.i0) * kC1 + fq * 4; c.k1 = (base + (unsigned)r.i1) * kC1 + fq * 4; c.k2 = (base + (unsigned)r.i2) * kC1 + fq * 4;
@@ -145,7 +148,7 @@ __global__ void __launch_bounds__(256, kD <= 4 ? 3 : 2) fp_table_head_kernel(con
             }
         }
         __builtin_amdgcn_sched_barrier(0);
-        const bool row_ok = tile * 16 + fi < a.rows;
+        const bool row_ok = tile * 16 + fi < rows;
 #pragma unroll
         for (int ct = 0; ct < kT2; ++ct) {
             const f32x4 sc = *reinterpret_cast<const f32x4 *>(s_sc2 + ct * 16 + fq * 4), sh = *reinterpret_cast<const f32x4 *>(s_sh2 + ct * 16 + fq * 4);
@@ -193,7 +196,7 @@ __global__ void __launch_bounds__(256, kD <= 4 ? 3 : 2) fp_table_head_kernel(con
                 if (a.relu4) y = fmaxf(y, 0.f);
                 // the row's original position sits in lane (row & 15) of cur.orow: rows 4 fq + r of this lane
                 const int orow = __builtin_amdgcn_ds_bpermute((fq * 4 + r) << 2, cur.orow);
-                if (fi < a.cout4 && tile * 16 + fq * 4 + r < a.rows) a.out[(size_t)orow * a.ldo + fi] = y;
+                if (fi < a.cout4 && tile * 16 + fq * 4 + r < rows) a.out[(size_t)orow * a.ldo + fi] = y;
             }
         }
         }   // HEAD
@@ -225,7 +228,7 @@ int g4d::fp_table_try(const StackCall &c, hipStream_t st) {
                 "g4d_mlp_chain_table_f32: null pointer");
     G4D_REQUIRE((alone || in.ldo >= c.Cout[2]) && tap_ld >= c.Cout[0], "g4d_mlp_chain_table_f32: output row stride %d or tap stride %d too small", in.ldo, tap_ld);
     FpTabArgs a;
-    a.rows = (int)c.rows; a.n = in.n; a.m = in.m; a.tab = in.known_feats; a.dist2 = in.dist2; a.nn_idx = in.nn_idx;
+    a.rows = (int)c.rows; a.live = live_for_clouds(c.rows / in.n, in.n); a.n = in.n; a.m = in.m; a.tab = in.known_feats; a.dist2 = in.dist2; a.nn_idx = in.nn_idx;
     a.perm_rec = cell_records(c, &a.perm_stride);
     const unsigned char *perm_rec = a.perm_rec;
     a.ps = in.pre_scale; a.pf = in.pre_shift;

@@ -146,7 +146,8 @@ __global__ void __launch_bounds__(64 * W) fps_reg_kernel(int n, int m, int bs, i
 // on the m1 = 64 UB picked points in pick order; same arithmetic, same tie-breaks, same outputs as the two launches.
 template <int UA, int UB, int FM>
 __global__ void __launch_bounds__(256) fps_reg_pair_kernel(int m2, const float *__restrict__ xyz_all, int *__restrict__ idx1_all,
-                                                          float *__restrict__ nx1_all, int *__restrict__ idx2_all, float *__restrict__ nx2_all) {
+                                                          float *__restrict__ nx1_all, int *__restrict__ idx2_all, float *__restrict__ nx2_all, const LiveRows live) {
+    if ((int)blockIdx.x >= live_clouds(live, (int)gridDim.x)) return;   // a dead cloud of a live-cloud scope: before the first load and barrier
     constexpr int T = 256, W = 4, nA = T * UA, bsA = nA, m1 = 64 * UB, bsB = m1;
     constexpr int log2bsA = UA == 1 ? 8 : (UA == 2 ? 9 : 10), log2bsB = UB == 1 ? 6 : (UB == 2 ? 7 : (UB == 4 ? 8 : 9));
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -469,7 +470,7 @@ extern "C" int g4d_fps_gather_pair_f32(int b, int n, int m1, int m2, const float
     G4D_REQUIRE(xyz && idx1 && new_xyz1 && idx2 && new_xyz2, "g4d_fps_gather_pair_f32: null pointer");
     const size_t lds = 2 * 16 * 16 + (size_t)n * 12 + (size_t)m1 * 16 + (size_t)m2 * 4;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    G4D_WITH_FM(distance_contraction(), hipLaunchKernelGGL((fps_reg_pair_kernel<4, 4, FM>), dim3(b), dim3(256), lds, s, m2, xyz, idx1, new_xyz1, idx2, new_xyz2))
+    G4D_WITH_FM(distance_contraction(), hipLaunchKernelGGL((fps_reg_pair_kernel<4, 4, FM>), dim3(b), dim3(256), lds, s, m2, xyz, idx1, new_xyz1, idx2, new_xyz2, live_for_clouds(b, m1)))
     return check_launch("g4d_fps_gather_pair_f32");
 }
 

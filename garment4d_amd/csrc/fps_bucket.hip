@@ -664,7 +664,9 @@ static int fps_kcap() {   // tuning hook: at most this many samples per round
 template <int FM, int KMAX>
 __global__ void __launch_bounds__(1024) fps_bucket_grid_kernel(int b, int n, int m, int bs, int log2bs, int deal, int pick_off,
                                                               const float *__restrict__ xyz_all, int *__restrict__ idx_all, float *__restrict__ nx_all,
-                                                              int cmax, float cell_req, unsigned char *__restrict__ ws_all, size_t ws_stride) {
+                                                              int cmax, float cell_req, unsigned char *__restrict__ ws_all, size_t ws_stride, const LiveRows live) {
+    // a dead cloud of a live-cloud scope, in either role: the workgroup leaves before its first load and frees its registers and LDS
+    if (((int)blockIdx.x < b ? (int)blockIdx.x : (int)blockIdx.x - b) >= live_clouds(live, b)) return;
     if ((int)blockIdx.x < b) fps_bucket_body<16, 8, FM, KMAX, true>(n, m, bs, log2bs, deal, pick_off, xyz_all, nullptr, idx_all, nx_all, blockIdx.x);
     else ball_grid_build_body(n, cmax, cmax, cell_req, xyz_all, ws_all, ws_stride, (int)blockIdx.x - b);
 }
@@ -672,7 +674,8 @@ __global__ void __launch_bounds__(1024) fps_bucket_grid_kernel(int b, int n, int
 template <int FM, int KMAX>
 __global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(7, 8)))
 fps_bucket_grid_reg_kernel(int b, int n, int m, int bs, int log2bs, int deal, int pick_off, const float *__restrict__ xyz_all, int *__restrict__ idx_all,
-                           float *__restrict__ nx_all, int cmax, float cell_req, unsigned char *__restrict__ ws_all, size_t ws_stride) {
+                           float *__restrict__ nx_all, int cmax, float cell_req, unsigned char *__restrict__ ws_all, size_t ws_stride, const LiveRows live) {
+    if (((int)blockIdx.x < b ? (int)blockIdx.x : (int)blockIdx.x - b) >= live_clouds(live, b)) return;   // (as in fps_bucket_grid_kernel)
     if ((int)blockIdx.x < b) fps_bucket_body<16, 8, FM, KMAX, false>(n, m, bs, log2bs, deal, pick_off, xyz_all, nullptr, idx_all, nx_all, blockIdx.x);
     else ball_grid_build_body(n, cmax, cmax, cell_req, xyz_all, ws_all, ws_stride, (int)blockIdx.x - b);
 }
@@ -729,9 +732,10 @@ int fps_bucket_grid_launch(int b, int n, int m, int bs, int log2bs, const float 
     G4D_WITH_FM(mode, k = multi ? (soa ? reinterpret_cast<const void *>(fps_bucket_grid_kernel<FM, kFpsPicks>) : reinterpret_cast<const void *>(fps_bucket_grid_reg_kernel<FM, kFpsPicks>))
                                 : reinterpret_cast<const void *>(fps_bucket_grid_kernel<FM, 1>))
     if (const int rc = ensure_dynamic_lds(k, 160 * 1024 - 1024, attr[slot], "g4d_fps_gather_grid_f32")) return rc;
+    const LiveRows live = live_for_clouds(b, m);
 #define G4D_GRID_LAUNCH(KM, KERN)                                                                                                                                    \
     G4D_WITH_FM(mode, hipLaunchKernelGGL((KERN<FM, KM>), dim3(2 * b), dim3(1024), lds, s, b, n, m, bs, log2bs, P | (fps_kcap() << 8), (int)pick_off, xyz, idx, nx, \
-                                         cmax, rmax * kCellSlack, reinterpret_cast<unsigned char *>(grid_ws), grid_cloud_bytes(n)))
+                                         cmax, rmax * kCellSlack, reinterpret_cast<unsigned char *>(grid_ws), grid_cloud_bytes(n), live))
     if (multi && soa) { G4D_GRID_LAUNCH(kFpsPicks, fps_bucket_grid_kernel) } else if (multi) { G4D_GRID_LAUNCH(kFpsPicks, fps_bucket_grid_reg_kernel) } else { G4D_GRID_LAUNCH(1, fps_bucket_grid_kernel) }
 #undef G4D_GRID_LAUNCH
     return check_launch("g4d_fps_gather_grid_f32");

@@ -66,6 +66,21 @@ long long tuning(const char *key, long long dflt);   // api.hip: run-time switch
 int distance_contraction();  // api.hip: the process-wide G4D_CONTRACT_* mode (0, 1 or 2)
 inline int knn_shape(int mode) { return mode == 0 ? 0 : 2; }  // the accumulate loop contracts to the chain shape
 
+// ---- live-cloud scope (include/g4d_live.h): what a launcher hands to a kernel whose launch is cloud-major.  count == nullptr: no scope applies,
+// every row is live -- the kernels then run exactly as without the scope.
+struct LiveRows { const int *count; int cap; int per_cloud; };   // device pointer to the live-cloud count | clouds of the launch | rows per cloud
+LiveRows live_for_clouds(long long b, long long rows_per_cloud);   // api.hip: applies when the calling thread's scope is open and b == its capacity
+LiveRows live_for_rows(long long rows);                            // ... and, for rows-only entry points, when rows % capacity == 0
+// live clouds / rows of a launch of b clouds / `rows` rows: the count read ONCE (uniform, on the scalar unit), clamped to [0, cap]
+__device__ __forceinline__ int live_clouds(const LiveRows &l, int b) {
+    if (!l.count) return b;
+    return min(max(__builtin_amdgcn_readfirstlane(*l.count), 0), l.cap);
+}
+__device__ __forceinline__ int live_rows(const LiveRows &l, int rows) {
+    if (!l.count) return rows;
+    return min(max(__builtin_amdgcn_readfirstlane(*l.count), 0), l.cap) * l.per_cloud;
+}
+
 // run `body` with a compile-time FM equal to the run-time `fm`
 #define G4D_WITH_FM(fm, ...)                                   \
     switch (fm) {                                              \

@@ -18,8 +18,11 @@ namespace g4d {
 
 // NK 16-wide k-steps, NC 16-channel tiles (K = 16 NK, Cout = 16 NC), NW waves per workgroup, OCC workgroups per CU (by LDS)
 template <int NK, int NC, int NW, int OCC>
-__global__ void __launch_bounds__(64 * NW, OCC) gemm_narrow_kernel(const LinearArgs a, int ntile) {
+__global__ void __launch_bounds__(64 * NW, OCC) gemm_narrow_kernel(const LinearArgs a) {
     extern __shared__ __attribute__((aligned(16))) float gn_smem[];
+    const int rows = live_rows(a.live, a.rows);      // under a live-cloud scope: the live clouds' rows
+    const int ntile = (rows + 15) / 16;
+    if ((int)blockIdx.x * NW >= ntile) return;       // no tile for this workgroup: it leaves before the weight copy
     float *s_w = gn_smem;                            // [ct][ks][lane][4]
     float *s_sc = gn_smem + NC * NK * 256, *s_sh = s_sc + 16 * NC;
     const int tid = threadIdx.x;
@@ -34,7 +37,7 @@ __global__ void __launch_bounds__(64 * NW, OCC) gemm_narrow_kernel(const LinearA
     }
     __syncthreads();
     auto load_x = [&](int tile, f32x4 (&x)[NK]) {
-        const float *p = a.X + (size_t)min(min(tile, ntile - 1) * 16 + fi, a.rows - 1) * a.ldx + fq * 4;   // past the end: clamped, never stored
+        const float *p = a.X + (size_t)min(min(tile, ntile - 1) * 16 + fi, rows - 1) * a.ldx + fq * 4;   // past the end: clamped, never stored
 #pragma unroll
         for (int ks = 0; ks < NK; ++ks) x[ks] = *reinterpret_cast<const f32x4 *>(p + ks * 16);
     };
@@ -54,7 +57,7 @@ __global__ void __launch_bounds__(64 * NW, OCC) gemm_narrow_kernel(const LinearA
                 for (int e = 0; e < 4; ++e) acc[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[e], x[ks][e], acc[ct], 0, 0, 0);
             }
         const int row = tile * 16 + fi;
-        float *o = a.out + (size_t)min(row, a.rows - 1) * a.ldo + a.col0 + fq * 4;
+        float *o = a.out + (size_t)min(row, rows - 1) * a.ldo + a.col0 + fq * 4;
 #pragma unroll
         for (int ct = 0; ct < NC; ++ct) {
             const f32x4 sc = *reinterpret_cast<const f32x4 *>(s_sc + ct * 16 + fq * 4), sh = *reinterpret_cast<const f32x4 *>(s_sh + ct * 16 + fq * 4);
@@ -64,7 +67,7 @@ __global__ void __launch_bounds__(64 * NW, OCC) gemm_narrow_kernel(const LinearA
                 y[r] = __builtin_fmaf(acc[ct][r], sc[r], sh[r]);
                 if (a.relu) y[r] = fmaxf(y[r], 0.f);
             }
-            if (row < a.rows) *reinterpret_cast<f32x4 *>(o + ct * 16) = y;
+            if (row < rows) *reinterpret_cast<f32x4 *>(o + ct * 16) = y;
         }
     };
     int tile = wg;
@@ -87,7 +90,7 @@ static int gemm_narrow_launch(const LinearArgs &a, hipStream_t s) {
     int dev = 0, cus = 256;
     if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     const long long want = ((long long)ntile + NW - 1) / NW, cap = (long long)OCC * cus;   // persistent: OCC workgroups per CU
-    hipLaunchKernelGGL((gemm_narrow_kernel<NK, NC, NW, OCC>), dim3((unsigned)(want < cap ? want : cap)), dim3(64 * NW), lds, s, a, ntile);
+    hipLaunchKernelGGL((gemm_narrow_kernel<NK, NC, NW, OCC>), dim3((unsigned)(want < cap ? want : cap)), dim3(64 * NW), lds, s, a);
     return check_launch("g4d_linear_f32(narrow)");
 }
 

@@ -59,6 +59,11 @@ __global__ void __launch_bounds__(128 * WN, WN) gemm_tile_kernel(const LinearArg
     // column blocks of a row block back to back.  The numbering rounds the row blocks up to a multiple of 8: a block past the last row block is
     // contracted on clamped rows like any other and stores nothing.
     const int G = gridDim.x;
+    // under a live-cloud scope: the live clouds' rows, and the blocks that hold them -- the numbering runs row group by row group, so the blocks
+    // past the last live group of 8 row blocks are exactly the tail of the range.  A workgroup without a block leaves before its first load.
+    const int rows = live_rows(a.live, a.rows);
+    nblocks = min(nblocks, (((rows + TM - 1) / TM + 7) / 8) * 8 * ncol_blk);
+    if ((int)blockIdx.x >= nblocks) return;
     auto place = [&](int b, int &r0, int &c0) {
         const int x = b & 7, slot = b >> 3;
         r0 = ((slot / ncol_blk) * 8 + x) * TM;
@@ -90,7 +95,7 @@ __global__ void __launch_bounds__(128 * WN, WN) gemm_tile_kernel(const LinearArg
         place((int)blockIdx.x + min(j, ntile - 1) * G, r0, c0);
 #pragma unroll
         for (int p = 0; p < P; ++p) {
-            fx[p] = a.X + (size_t)min(r0 + lr + RS * p, a.rows - 1) * a.ldx + lk;     // rows past the end: clamped, never stored
+            fx[p] = a.X + (size_t)min(r0 + lr + RS * p, rows - 1) * a.ldx + lk;     // rows past the end: clamped, never stored
             fw[p] = a.W + (size_t)min(c0 + lr + RS * p, cpad - 1) * a.Kpad + lk;      // channels past the padded width: clamped, never stored
         }
     };
@@ -131,7 +136,7 @@ __global__ void __launch_bounds__(128 * WN, WN) gemm_tile_kernel(const LinearArg
         if constexpr (TAB) {   // g4d_linear_interp_add_f32: the rows' interpolation contexts, formed ahead of the contraction
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const InterpRow r = interp_row(a, min(row0 + wr * 64 + i * 16 + fi, a.rows - 1));
+                const InterpRow r = interp_row(a, min(row0 + wr * 64 + i * 16 + fi, rows - 1));
                 ctx[i] = Ctx{r.w0, r.w1, r.w2, (unsigned)r.k0, (unsigned)r.k1, (unsigned)r.k2};
             }
         }
@@ -178,7 +183,7 @@ __global__ void __launch_bounds__(128 * WN, WN) gemm_tile_kernel(const LinearArg
                 y[r] = __builtin_fmaf(y[r], sc[j][r], sh[j][r]);
                 if (a.relu) y[r] = fmaxf(y[r], 0.f);
             }
-            if (FULL || row < a.rows) {
+            if (FULL || row < rows) {
                 float *o = a.out + (size_t)row * a.ldo + a.col0 + ch0;
                 if constexpr (VEC) *reinterpret_cast<f32x4 *>(o) = y;          // (Cout is a multiple of 128: the four channels are inside the row)
                 else {
@@ -247,7 +252,7 @@ __global__ void __launch_bounds__(128 * WN, WN) gemm_tile_kernel(const LinearArg
         cur ^= 1;
         if (++c == nchunk) {
             if (vec) {
-                if (row0 + TM <= a.rows) epilogue(std::true_type{}, std::true_type{});
+                if (row0 + TM <= rows) epilogue(std::true_type{}, std::true_type{});
                 else epilogue(std::false_type{}, std::true_type{});
             } else epilogue(std::false_type{}, std::false_type{});
             c = 0;

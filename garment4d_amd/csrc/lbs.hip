@@ -457,7 +457,8 @@ typedef float mf_f2 __attribute__((ext_vector_type(2)));
 __global__ void __launch_bounds__(256) lbs_frame_kernel(int B, int J, int NB, int JS, int pose2rot, const float *__restrict__ betas, int betas_bstride,
                                                         const float *__restrict__ pose, const float *__restrict__ Jt, const float *__restrict__ Js,
                                                         const int *__restrict__ parents, float *__restrict__ A_out, float *__restrict__ posed_joints,
-                                                        float *__restrict__ Cws, float *__restrict__ Aws) {
+                                                        float *__restrict__ Cws, float *__restrict__ Aws, const LiveRows live) {
+    B = live_clouds(live, B);   // under a live-cloud scope (frames counted as clouds): the live frames
     __shared__ float sR_[4][kOneJ * 9], sJ_[4][kOneJ * 3], sL_[4][kOneJ * 12], sG_[4][kOneJ * 12], sC_[4][4 * kMfKS];
     const int l = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int b = blockIdx.x * 4 + w;
@@ -550,7 +551,9 @@ __global__ void __launch_bounds__(256) lbs_frame_kernel(int B, int J, int NB, in
 template <int JS>
 __global__ void __launch_bounds__(64 * kMfWaves) lbs_mfma_kernel(int B, int V, int J, int NC, const float *__restrict__ v_template,
                                                                 const float *__restrict__ blend_dirs, const float *__restrict__ weights,
-                                                                const float *__restrict__ Cws, const float *__restrict__ Aws, float *__restrict__ verts) {
+                                                                const float *__restrict__ Cws, const float *__restrict__ Aws, float *__restrict__ verts, const LiveRows live) {
+    B = live_clouds(live, B);   // under a live-cloud scope (frames counted as clouds): the live frames
+    if (B <= 0) return;         // none: the unit clamps below would go negative -- before the first load and barrier
     extern __shared__ __attribute__((aligned(16))) float mf_smem[];   // [2 halves][3 coords][14 groups][4 q][16 vertices][4 k-steps]
     constexpr int KG = kMfKS / 4;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -838,8 +841,9 @@ extern "C" int g4d_lbs_mfma_f32(int b, int v, int j, int nb, int pose2rot, const
     G4D_REQUIRE(ws_bytes >= g4d_lbs_mfma_ws_bytes(b, j) && (reinterpret_cast<uintptr_t>(ws) & 15) == 0, "g4d_lbs_mfma_f32: workspace too small or not 16-byte aligned");
     const int js = j <= 24 ? 6 : 8;
     float *Cws = reinterpret_cast<float *>(ws), *Aws = Cws + (size_t)((b + 15) / 16) * 16 * 4 * kMfKS;
+    const LiveRows live = live_for_clouds(b, v);
     hipLaunchKernelGGL(lbs_frame_kernel, dim3((b + 3) / 4), dim3(256), 0, G4D_S(stream), b, j, nb, js, pose2rot, betas, betas_bstride, pose, J_template,
-                       J_shapedirs, parents, A_out, posed_joints, Cws, Aws);
+                       J_shapedirs, parents, A_out, posed_joints, Cws, Aws, live);
     if (const int rc = check_launch("g4d_lbs_mfma_f32(frames)")) return rc;
     const int lds = (int)sizeof(float) * (2 * 3 * (kMfKS / 4) * 256 + 2 * js * 64 + kMfVT * 3 + 32);   // 86 KB of blend rows + weights + template
     const int nc = nb + (j - 1) * 9;
@@ -847,12 +851,12 @@ extern "C" int g4d_lbs_mfma_f32(int b, int v, int j, int nb, int pose2rot, const
         static unsigned long long attr = 0;
         if (const int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(lbs_mfma_kernel<6>), lds, attr, "g4d_lbs_mfma_f32")) return rc;
         hipLaunchKernelGGL(lbs_mfma_kernel<6>, dim3((v + kMfVT - 1) / kMfVT), dim3(64 * kMfWaves), lds, G4D_S(stream), b, v, j, nc, v_template, blend_dirs,
-                           lbs_weights, Cws, Aws, verts);
+                           lbs_weights, Cws, Aws, verts, live);
     } else {
         static unsigned long long attr = 0;
         if (const int rc = ensure_dynamic_lds(reinterpret_cast<const void *>(lbs_mfma_kernel<8>), lds, attr, "g4d_lbs_mfma_f32")) return rc;
         hipLaunchKernelGGL(lbs_mfma_kernel<8>, dim3((v + kMfVT - 1) / kMfVT), dim3(64 * kMfWaves), lds, G4D_S(stream), b, v, j, nc, v_template, blend_dirs,
-                           lbs_weights, Cws, Aws, verts);
+                           lbs_weights, Cws, Aws, verts, live);
     }
     return check_launch("g4d_lbs_mfma_f32");
 }

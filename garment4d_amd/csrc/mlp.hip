@@ -44,8 +44,11 @@ __device__ __forceinline__ f32x4 load4(const LinearArgs &a, const RowCtx<MODE> &
 // MT = accumulator tiles per wave: block tile = (16*MT) rows x 64 channels.  MT=4 for big row counts, MT=2 when the
 // launch would otherwise leave CUs idle (few rows, wide layers: the FP levels).
 template <int MODE, int MT>
-__global__ void __launch_bounds__(256) linear_kernel(const LinearArgs a) {
+__global__ void __launch_bounds__(256) linear_kernel(const LinearArgs a_) {
     constexpr int BM = 16 * MT;
+    LinearArgs a = a_;
+    a.rows = live_rows(a_.live, a_.rows);            // under a live-cloud scope: the live clouds' rows
+    if ((int)blockIdx.x * BM >= a.rows) return;      // a row block of dead clouds: leaves before its first load and barrier
     __shared__ __attribute__((aligned(16))) float sA[2][BM * LDT];
     __shared__ __attribute__((aligned(16))) float sB[2][BN * LDT];
     const int t = threadIdx.x;
@@ -295,6 +298,8 @@ extern "C" int g4d_linear_f32(long long rows, int K, int Kpad, int Cout, const f
     LinearArgs a = {};
     a.rows = (int)rows; a.K = K; a.Kpad = Kpad; a.Cout = Cout; a.W = W; a.scale = scale; a.shift = shift; a.relu = relu;
     a.out = out; a.ldo = ldo; a.col0 = col0; a.pool = pool; a.S = pool ? s_pool : 1; a.X = X; a.ldx = ldx;
+    a.live = live_for_rows(rows);                    // rows only: cloud-major when the open scope's capacity divides them
+    if (pool && a.live.count && a.live.per_cloud % s_pool != 0) a.live = {nullptr, 0, 0};   // (a pooling window never spans clouds)
     return launch_linear(LOAD_DIRECT, a, reinterpret_cast<hipStream_t>(stream));
 }
 
@@ -309,6 +314,7 @@ extern "C" int g4d_linear_interp_add_f32(long long rows, int n, int m, int K, in
     a.rows = (int)rows; a.K = K; a.Kpad = Kpad; a.Cout = Cout; a.W = W; a.scale = scale; a.shift = shift; a.relu = relu;
     a.out = out; a.ldo = ldo; a.col0 = col0; a.pool = 0; a.S = 1; a.X = X; a.ldx = ldx;
     a.tab = table; a.tab_ld = tab_ld; a.dist2 = dist2; a.nn_idx = nn_idx; a.n = n; a.m = m;
+    a.live = live_for_clouds(rows / n, n);
     return launch_linear(LOAD_DIRECT, a, reinterpret_cast<hipStream_t>(stream));
 }
 

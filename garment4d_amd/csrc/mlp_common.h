@@ -54,6 +54,9 @@ struct LinearArgs {
     // original index kept in the 4th dword of the cloud's 16-byte grid records (perm_rec + cloud * perm_stride bytes).  NULL: rows in place.
     const unsigned char *perm_rec;
     size_t perm_stride;
+    // live-cloud scope of the launch (g4d_common.h; count == nullptr: none).  Honoured by linear_kernel, gemm_narrow_kernel and gemm_tile_kernel;
+    // every other kernel that takes a LinearArgs ignores it and computes all rows.
+    LiveRows live;
 };
 
 // output / skip row of launch row `row` (see LinearArgs::perm_rec)

@@ -40,6 +40,9 @@ struct SaTabArgs {
     // nullptr: the static partition of rounds 4-5 (every block of every neighbourhood)
     const int *items, *wg_len;
     int cap;
+    // live-cloud scope of the launch (count == nullptr: none).  The lock-step form (WM == 2) never carries one: with a work list the count is
+    // read by the pre-pass alone and the main kernel takes its work from the lists that wrote; without a list it computes every cloud.
+    LiveRows live;
 };
 
 // ---- work list of the lock-step kernel (round 6).  A neighbourhood of S = 64 samples is four 16-row blocks, and ball_query pads it with copies
@@ -61,9 +64,13 @@ constexpr int kItemFirst = 1 << 28, kItemLast = 1 << 29, kItemDead = 1 << 30, kI
 // kernel 16 us long).
 constexpr int kCountWaves = 16;
 template <int S>
-__global__ void __launch_bounds__(64 * kCountWaves) sa_units_count_kernel(int nq, int nq_cap, const int *__restrict__ idx, int *__restrict__ counts, int *__restrict__ order) {
+__global__ void __launch_bounds__(64 * kCountWaves) sa_units_count_kernel(int nq_cap, const LiveRows live_q, const int *__restrict__ idx, int *__restrict__ counts, int *__restrict__ order) {
     constexpr int G = S / 16, UPL = 64 / S;          // neighbourhoods per 64-lane load
     __shared__ int s_cnt[kCountWaves][4], s_base[4];
+    // neighbourhoods of the live clouds (live_q counts in neighbourhoods per cloud; no scope: all nq_cap).  THE place where the lock-step stack
+    // reads the count: the lists written here are what the items kernel and the main kernel work from.
+    const int nq = live_rows(live_q, nq_cap);
+    if ((int)blockIdx.x * (64 * kCountWaves) >= nq) return;   // no neighbourhood for this workgroup (none at all: the clamp below would go negative)
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, wave = blockIdx.x * kCountWaves + wv;
     const int q0 = wave * 64;                        // this wave's 64 neighbourhoods: lane l keeps nb of neighbourhood q0 + l
     int mine = 0;
@@ -172,6 +179,11 @@ __global__ void __launch_bounds__(256, (WM == 1 && C == 64 && S == 32 && G4D_SA6
     float *s_w2 = smem + NCONST, *s_w3 = s_w2 + NW2;
     float *s_stage = smem + NCONST;                  // WM == 2: [2][kStageK * T3 * 256] floats: two buffers of one chunk's fragments
     const int tid = threadIdx.x;
+    const int rows = live_rows(a.live, a.rows);      // under a live-cloud scope: the live clouds' rows (WM == 2: always a.rows, see SaTabArgs)
+    const int nblk = (rows + R - 1) / R;             // 16 MT-row blocks of the launch
+    const int nunit = (nblk + G - 1) / G;            // a wave's unit of work: G consecutive blocks = whole neighbourhoods
+    // a workgroup without work leaves before its first load and barrier: an empty item list, or no unit for its first wave
+    if (WM == 2 && a.items != nullptr ? a.wg_len[blockIdx.x] == 0 : (int)blockIdx.x * 4 >= nunit) return;
     for (int i = tid; i < 3 * C; i += 256) s_wx[i] = a.wx[i];
     for (int i = tid; i < C; i += 256) { s_ps[i] = a.ps[i]; s_pf[i] = a.pf[i]; s_sc2[i] = a.sc2[i]; s_sh2[i] = a.sh2[i]; }
     for (int i = tid; i < 2 * C; i += 256) { s_sc3[i] = a.sc3[i]; s_sh3[i] = a.sh3[i]; }
@@ -189,10 +201,8 @@ __global__ void __launch_bounds__(256, (WM == 1 && C == 64 && S == 32 && G4D_SA6
 
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // (uniform: block numbers, copy sources and destinations on the scalar unit)
     const int fi = lane & 15, fq = lane >> 4;
-    const int nblk = (a.rows + R - 1) / R;           // 16 MT-row blocks of the launch
-    const int nunit = (nblk + G - 1) / G;            // a wave's unit of work: G consecutive blocks = whole neighbourhoods
     const int nwaves = gridDim.x * 4, wg = blockIdx.x * 4 + wave;
-    const int nq = a.rows / S;
+    const int nq = rows / S;
 
     // WM == 2 with a work list: the items of iterations it .. it + 3 (item 3 in flight), shifted at the end of every iteration
     const bool listed = WM == 2 && a.items != nullptr;
@@ -212,7 +222,7 @@ __global__ void __launch_bounds__(256, (WM == 1 && C == 64 && S == 32 && G4D_SA6
     struct Rows { f32x4 raw[T][MT]; float px[MT], py[MT], pz[MT], cx[MT], cy[MT], cz[MT]; };
     auto load_idx = [&](int blk, int (&v)[MT]) {
 #pragma unroll
-        for (int mt = 0; mt < MT; ++mt) v[mt] = a.idx[min(blk * R + mt * 16 + fi, a.rows - 1)];
+        for (int mt = 0; mt < MT; ++mt) v[mt] = a.idx[min(blk * R + mt * 16 + fi, rows - 1)];
     };
     // The rows of a block: rows_begin() forms the table-row pointers and requests the coordinates (small loads); the T * MT 16-byte table loads --
     // the expensive ones at the CU's 64 B / clk vector-memory path -- are requested ONE AT A TIME by rows_raw(q), which the block loop calls
@@ -582,12 +592,14 @@ static int sa_table_launch(SaTabArgs a, hipStream_t st, void *ws = nullptr, long
     const unsigned grid = (unsigned)(want < cap ? want : cap);
     a.items = nullptr; a.wg_len = nullptr; a.cap = 0;
     if constexpr (WM == 2) {
+        const LiveRows live_q = {a.live.count, a.live.cap, a.live.per_cloud / S};   // the scope in neighbourhoods per cloud, for the pre-pass
+        a.live = {nullptr, 0, 0};
         const long long nq = a.rows / S;
         if (ws && tuning("sa_table_dedup", 1) && a.rows % S == 0 && grid <= (unsigned)kListWgMax && ws_bytes >= list_bytes(nq, G) && nq * G < (1ll << 28)) {
             int *counts = reinterpret_cast<int *>(ws), *order = counts + 8, *wg_len = order + (size_t)G * nq, *items = wg_len + kListWgMax;
             const long long icap = list_cap(nq, G, grid);
             if (hipMemsetAsync(counts, 0, 32, st) != hipSuccess) return check_launch("g4d_sa_table(work list)");
-            hipLaunchKernelGGL((sa_units_count_kernel<S>), dim3((unsigned)(((nq + 63) / 64 + kCountWaves - 1) / kCountWaves)), dim3(64 * kCountWaves), 0, st, (int)nq, (int)nq, a.idx, counts, order);
+            hipLaunchKernelGGL((sa_units_count_kernel<S>), dim3((unsigned)(((nq + 63) / 64 + kCountWaves - 1) / kCountWaves)), dim3(64 * kCountWaves), 0, st, (int)nq, live_q, a.idx, counts, order);
             hipLaunchKernelGGL(sa_units_items_kernel, dim3((grid * 4 + 255) / 256), dim3(256), 0, st, G, (int)nq, (int)grid, (int)icap, counts, order, items, wg_len);
             if (const int rc = check_launch("g4d_sa_table(work list)")) return rc;
             a.items = items; a.wg_len = wg_len; a.cap = (int)icap;
@@ -636,6 +648,7 @@ int g4d::sa_table_try(const StackCall &c, hipStream_t st) {
     a.W2 = W[0]; a.sc2 = c.scale[0]; a.sh2 = c.shift[0];
     a.W3 = W[1]; a.sc3 = c.scale[1]; a.sh3 = c.shift[1];
     a.out = in.out; a.ldo = in.ldo; a.col0 = in.col0;
+    a.live = live_for_clouds(c.rows / ((long long)in.P * S), (long long)in.P * S);   // (rows = clouds x P x S: required above)
     if (Kt == 32 && S == 16) return sa_table_launch<32, 16, 2, 1>(a, st);
     if (Kt == 32 && S == 32) return sa_table_launch<32, 32, 2, 1>(a, st);
     if (Kt == 64 && S == 32) return sa_table_launch<64, 32, 2, 1>(a, st);

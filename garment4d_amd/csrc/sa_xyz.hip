@@ -36,6 +36,7 @@ struct SaXyzArgs {
     int kst2, kst3;
     float *out;
     int ldo, col0;
+    LiveRows live;                    // live-cloud scope of the launch (count == nullptr: none)
 };
 
 // One stack over the passes `first, first + stride, ...` of a wave (a pass = 32 consecutive grouped rows).  LOGS / MAXP are compile-time:
@@ -50,6 +51,9 @@ __device__ __forceinline__ void sa_xyz_body(const SaXyzArgs &a, int first, int s
     static_assert(T3 == 2 || T3 == 4, "32 or 64 output channels");
     const int lane = threadIdx.x & 63;
     const int fi = lane & 15, fq = lane >> 4;
+    const int rows = live_rows(a.live, (int)a.rows);   // < 2^31 (launcher); under a live-cloud scope: the live clouds' rows
+    const int npass = (rows + 31) >> 5;      // 32 rows per pass; S = 16 divides it, S = 32 is it
+    if (first >= npass) return;              // nothing for this wave (no live row at all: the clamps below would go negative) -- before its first load
     // ---- weights into registers, once per wave
     float w1f[T1], s1[T1][4], h1s[T1][4];   // w1f: A fragment of layer 1, lane (channel fi, k = fq): W1[16 ks + fi][fq], 0 for the padding column k = 3
 #pragma unroll
@@ -82,8 +86,6 @@ __device__ __forceinline__ void sa_xyz_body(const SaXyzArgs &a, int first, int s
 #pragma unroll
     for (int ct = 0; ct < T3; ++ct) { s3[ct] = a.sc3[ct * 16 + fi]; h3s[ct] = a.sh3[ct * 16 + fi]; }
 
-    const int rows = (int)a.rows;            // < 2^31 (launcher)
-    const int npass = (rows + 31) >> 5;      // 32 rows per pass; S = 16 divides it, S = 32 is it
     // Two-level software pipeline over the wave's passes (the gather is two dependent loads: index -> coordinates): while pass k is on
     // the VALU / MFMA, the coordinates of pass k + 1 are in flight and so are the indices of pass k + 2.
     struct Rows { float px[2], pq[2]; };   // component cfq of the neighbour / of the centre
@@ -92,7 +94,7 @@ __device__ __forceinline__ void sa_xyz_body(const SaXyzArgs &a, int first, int s
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt) v[mt] = a.idx[min(min(pass, npass - 1) * 32 + mt * 16 + fi, rows - 1)];   // unconditional (see load_rows)
     };
-    const int nq = (int)(a.rows >> LOGS);
+    const int nq = rows >> LOGS;
     auto load_rows = [&](int pass, const int (&v)[2], Rows &rw) {
         // No `if (pass < npass)` around these loads: past the end the last pass is read again and never used.  A conditional block
         // makes the number of loads in flight unknown at the join, and the wait for the CURRENT pass's rows (older than these)
@@ -298,6 +300,7 @@ static int sa_xyz_fill(SaXyzArgs &a, int b, int n, int p, int nsample, const flo
     G4D_REQUIRE(kpad2 % 16 == 0 && kpad2 >= c1 && kpad3 % 16 == 0 && kpad3 >= c2, "g4d_sa_xyz_mlp3_f32: Kpad of layers 2 / 3 must be multiples of 16 covering c1 / c2");
     a.W2f = W2_frag; a.sc2 = scale2; a.sh2 = shift2; a.W3f = W3_frag; a.sc3 = scale3; a.sh3 = shift3; a.kst2 = kpad2 / 16; a.kst3 = kpad3 / 16;
     a.out = out; a.ldo = ldo; a.col0 = col0;
+    a.live = live_for_clouds(b, (long long)p * nsample);
     return G4D_OK;
 }
 
@@ -349,6 +352,7 @@ extern "C" int g4d_sa_xyz_mlp3_f32(int b, int n, int p, int nsample, const float
     G4D_REQUIRE(kpad2 % 16 == 0 && kpad2 >= c1 && kpad3 % 16 == 0 && kpad3 >= c2, "g4d_sa_xyz_mlp3_f32: Kpad of layers 2 / 3 must be multiples of 16 covering c1 / c2");
     a.W2f = W2_frag; a.sc2 = scale2; a.sh2 = shift2; a.W3f = W3_frag; a.sc3 = scale3; a.sh3 = shift3; a.kst2 = kpad2 / 16; a.kst3 = kpad3 / 16;
     a.out = out; a.ldo = ldo; a.col0 = col0;
+    a.live = live_for_clouds(b, (long long)p * nsample);
     const long long npass = (rows + 31) / 32, want = (npass + 3) / 4;
     static const int bpc = [] { const char *e = getenv("G4D_SA_XYZ_BLOCKS_PER_CU"); return e && atoi(e) > 0 ? atoi(e) : 3; }();
     const unsigned grid = (unsigned)(want < 256 * bpc ? want : 256 * bpc);   // persistent waves (3 per SIMD): the weights are loaded once per wave

@@ -45,7 +45,8 @@ constexpr size_t kPrBoxOff = (size_t)kPrM * 16, kPrCodeOff = kPrBoxOff + (size_t
 constexpr size_t kPrCloudBytes = kPrGridOff + 16;
 constexpr int kPrepT = 512;          // threads of the pre-pass: one compare-exchange pair each
 
-__global__ void __launch_bounds__(kPrepT) nn_prune_prep_kernel(int m, const float *__restrict__ known_all, unsigned char *__restrict__ ws) {
+__global__ void __launch_bounds__(kPrepT) nn_prune_prep_kernel(int m, const float *__restrict__ known_all, unsigned char *__restrict__ ws, const LiveRows live) {
+    if ((int)blockIdx.x >= live_clouds(live, (int)gridDim.x)) return;   // a dead cloud of a live-cloud scope: before the first load and barrier
     __shared__ unsigned long long keys[kPrM];
     __shared__ float sx[kPrM], sy[kPrM], sz[kPrM];
     __shared__ float red[6][kPrepT / 64];
@@ -131,7 +132,8 @@ constexpr int kPrT = 1024;   // queries (threads) per workgroup: one 23 KB stagi
 template <int FM>
 __global__ void __launch_bounds__(kPrT) three_nn_prune_kernel(int n, int m, const float *__restrict__ unknown_all, const unsigned char *__restrict__ ws,
                                                             float *__restrict__ dist2_all, int *__restrict__ idx_all,
-                                                            const unsigned char *__restrict__ qrec, size_t qstride, int sorted_out) {
+                                                            const unsigned char *__restrict__ qrec, size_t qstride, int sorted_out, const LiveRows live) {
+    if ((int)blockIdx.y >= live_clouds(live, (int)gridDim.y)) return;   // a dead cloud of a live-cloud scope: before the first load and barrier
     // 20 floats per block of 16 records: the per-lane reads of step 1 (lanes in different home blocks) would otherwise all fall into the two
     // banks a 64-byte block stride leaves; 16-byte alignment of a block's four-record groups is kept
     constexpr int LB = kPrBlk + 4;
@@ -253,7 +255,8 @@ extern "C" int g4d_three_nn_pruned_f32(int b, int n, int m, const float *unknown
     G4D_REQUIRE(known && dist2 && idx && ws && (unknown || unknown_grid) && (!sorted_out || unknown_grid), "g4d_three_nn_pruned_f32: null pointer");
     G4D_REQUIRE(ws_bytes >= g4d_three_nn_pruned_ws_bytes(b) && (reinterpret_cast<uintptr_t>(ws) & 15) == 0, "g4d_three_nn_pruned_f32: workspace too small or not 16-byte aligned");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(nn_prune_prep_kernel, dim3(b), dim3(kPrepT), 0, st, m, known, reinterpret_cast<unsigned char *>(ws));
+    const LiveRows live = live_for_clouds(b, n);
+    hipLaunchKernelGGL(nn_prune_prep_kernel, dim3(b), dim3(kPrepT), 0, st, m, known, reinterpret_cast<unsigned char *>(ws), live);
     if (const int rc = check_launch("g4d_three_nn_pruned_f32(prep)")) return rc;
     size_t off = 0, stride = 0;
     const unsigned char *qrec = nullptr;
@@ -263,6 +266,6 @@ extern "C" int g4d_three_nn_pruned_f32(int b, int n, int m, const float *unknown
     }
     dim3 grid((n + kPrT - 1) / kPrT, b);
     G4D_WITH_FM(distance_contraction(), hipLaunchKernelGGL((three_nn_prune_kernel<FM>), grid, dim3(kPrT), 0, st, n, m, unknown, reinterpret_cast<const unsigned char *>(ws), dist2, idx,
-                                                           qrec, stride, sorted_out))
+                                                           qrec, stride, sorted_out, live))
     return check_launch("g4d_three_nn_pruned_f32");
 }

@@ -17,8 +17,11 @@ shared-MLP launches of 8 clouds are one wave-round each (ramp + tail, no steady 
     logits, verts, joints = fut.result()         # waits for the step's call; views into the slot's output buffers
 
 The views stay valid until `streams` further calls have been launched (the slot is then reused); pass copy=True to result() to keep
-them.  A partially filled call is launched by flush() (or by result() on one of its steps): the graph then runs on the slot's
-stale tail clouds as well -- wasted work, never wrong results.
+them.  A partially filled call is launched by flush() (or by result() on one of its steps): the captured graph is replayed as it is, but
+every call is made inside a live-cloud scope (include/g4d_live.h) whose count -- one int per slot in device memory, rewritten on the slot's
+stream ahead of every launch -- tells the kernels how many of the slot's clouds are filled: the stale tail clouds are not computed (their
+output rows keep what an earlier call left there), the filled ones get the bits of a full call.  Without a graph (use_graph=False) a
+partially filled call is simply made on the filled clouds.
 
 hipGraph + streams: the HIP runtime maps streams onto the hardware queues the environment allows (GPU_MAX_HW_QUEUES).  Streams
 beyond that share queues: the calls still run, with less overlap between them.
@@ -59,7 +62,7 @@ class StepFuture:
 
 
 class _Slot:
-    __slots__ = ("stream", "cloud", "betas", "pose", "graph", "outs", "event", "fill", "gen", "launched_gen")
+    __slots__ = ("stream", "cloud", "betas", "pose", "graph", "outs", "event", "fill", "gen", "launched_gen", "live", "live_set")
 
 
 class StepPipeline:
@@ -88,28 +91,42 @@ class StepPipeline:
             s.pose = None if smpl is None else (torch.zeros((self.B * self.k, nj * 3), dtype=torch.float32, device=dev) if pose2rot else
                                                 torch.eye(3, device=dev).repeat(self.B * self.k, nj, 1, 1).contiguous())
             s.graph, s.outs, s.event = None, None, torch.cuda.Event()
+            # live clouds of the slot's next launch (device side of the live-cloud scope), and the values _launch() copies into it: one resident
+            # tensor per possible fill, so that a launch enqueues a 4-byte device-to-device copy and never touches pageable host memory
+            s.live = torch.full((1,), self.B * self.k, dtype=torch.int32, device=dev)
+            s.live_set = torch.arange(0, self.k + 1, dtype=torch.int32, device=dev) * self.B
             s.fill, s.gen, s.launched_gen = 0, 1, 0
             self.slots.append(s)
         self._cur = 0
         self._warm()
 
     # ---- one call = the hot path on a slot's 8 * coalesce clouds
-    def _call(self, s):
-        with _tuning.use(self.tuning):
-            return self._call_tuned(s)
+    def _call(self, s, fill=None):
+        """fill = None: the call on all of the slot's clouds, inside the slot's live-cloud scope (the warm-up, the capture, a full eager call).
+        fill = a number of steps (the eager path's partially filled call): the call on the first fill * B clouds themselves, without a scope --
+        launching on fewer clouds is what every kernel supports, bit-identical per cloud, and an eager call's intermediates are fresh
+        allocations, not the buffers of an earlier full call that the scope's skipped clouds may rely on."""
+        if fill is not None:
+            with _tuning.use(self.tuning):
+                return self._call_tuned(s, fill * self.B)
+        with _tuning.use(self.tuning), _lib.live_scope(s.live, self.B * self.k):
+            return self._call_tuned(s, self.B * self.k)
 
-    def _call_tuned(self, s):
+    def _call_tuned(self, s, nb):
+        cloud, betas, pose = s.cloud, s.betas, s.pose
+        if nb != self.B * self.k:
+            cloud, betas, pose = cloud[:nb], (None if betas is None else betas[:nb]), (None if pose is None else pose[:nb])
         if self.encoder_call is not None:
             from . import fused
             with fused.precision(self.precision):
-                logits = self.encoder_call(self.model, s.cloud)
+                logits = self.encoder_call(self.model, cloud)
             out = (None, logits)
         else:
-            out = self.model.forward_fused(s.cloud, precision=self.precision)
+            out = self.model.forward_fused(cloud, precision=self.precision)
         v = j = None
         if self.smpl is not None:
             P = self.smpl
-            v, j = G.lbs(s.betas, s.pose, P["v_template"], P["shapedirs"], P["posedirs"], P["J_regressor"], P["parents"], P["lbs_weights"],
+            v, j = G.lbs(betas, pose, P["v_template"], P["shapedirs"], P["posedirs"], P["J_regressor"], P["parents"], P["lbs_weights"],
                          pose2rot=self.pose2rot)
         return out[1], v, j
 
@@ -125,14 +142,22 @@ class StepPipeline:
                     with torch.cuda.graph(s.graph, stream=s.stream):
                         s.outs = self._call(s)
                 torch.cuda.synchronize(self.device)
+                # one full replay per slot: the capture computed nothing, and the graph's private buffers must hold valid, in-range values
+                # (neighbour indices above all) for every cloud before a partially filled replay leaves some of them untouched -- a kernel
+                # that does not honour the count computes the stale clouds from them, as every kernel did before the scope existed
+                for s in self.slots:
+                    with torch.cuda.stream(s.stream):
+                        s.graph.replay()
+                torch.cuda.synchronize(self.device)
 
     def _launch(self, s):
         with torch.cuda.stream(s.stream):
             if s.graph is not None:
+                s.live.copy_(s.live_set[s.fill:s.fill + 1], non_blocking=True)   # the filled clouds of this launch, ahead of it on the slot's stream
                 s.graph.replay()
             else:
                 with torch.no_grad():
-                    s.outs = self._call(s)
+                    s.outs = self._call(s, None if s.fill == self.k else s.fill)
             s.event.record(s.stream)
         s.launched_gen = s.gen
         s.gen += 1
